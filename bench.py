@@ -11,6 +11,17 @@ value is the WHOLE-JOB aggregate over all ranks.
 Single GPU:     python bench.py --gpus 1 --steps 30 --warmup 10
 Multi-GPU:      torchrun --nproc-per-node N bench.py --gpus N ...
                 (one rank per GPU over RCCL; reads RANK/WORLD_SIZE/MASTER_*)
+
+A plain run sets up, warms up, times ``--steps`` learner updates and prints
+one JSON line.  ``--dump-outputs DIR`` additionally writes what the last
+timed update returned (loss, per-sequence priorities) as ``DIR/<name>.npy``;
+seeds are fixed, so two builds run with the same arguments see the same
+inputs and can be compared output for output.  For the same reason the
+priorities written back to the GPU replay in the timed loop come from a
+seeded table, not from the step's own output, so which sequences are
+sampled never depends on the last bits of earlier steps.  ``--full`` is where any
+measurement beyond the headline figure belongs; the benchmark has none
+today, so it changes nothing yet.
 """
 
 import argparse
@@ -87,6 +98,20 @@ def build_synthetic_block(c, rng):
                  np.full(nseq, burn, dtype=np.uint8), learn_arr, fwd_arr)
 
 
+def dump_outputs(out_dir, loss, priorities):
+    """Write what the last timed train_step returned to its caller:
+    loss.npy (1,) and priorities.npy (batch,), both float32."""
+    def to_np(x):
+        if torch.is_tensor(x):
+            x = x.detach().float().cpu().numpy()
+        return np.asarray(x, dtype=np.float32)
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), to_np(loss).reshape(1))
+    np.save(os.path.join(out_dir, "priorities.npy"),
+            to_np(priorities).reshape(-1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -109,7 +134,16 @@ def main():
                     help="time prebuilt device batches instead")
     ap.add_argument("--replay-transitions", type=int, default=160_000,
                     help="synthetic transitions pre-filled into the GPU replay")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                    default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed "
+                         "step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (none exist "
+                         "yet: a plain run already does only what the "
+                         "headline figure needs)")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     from r2d2_amd import config as cfg
 
@@ -173,6 +207,19 @@ def main():
         for i in range(replay.num_blocks):
             replay.ingest(pool[i % len(pool)],
                           rng.random(replay.spb).astype(np.float32) + 0.1)
+        # Priorities written back in the timed loop: a fixed seeded table
+        # indexed by the sampled sequence (rotated per step), in the range
+        # of the prefill priorities.  Writing back the step's own
+        # priorities would make every later sample depend on the last bits
+        # of earlier outputs — the weight-gradient kernels accumulate with
+        # f32 atomics, so those bits vary from run to run, and one sample
+        # that lands on another sequence changes the whole batch.  With
+        # the table the sampled batches are the same in every run; the
+        # update kernel does the same work either way.  Keyed by sequence,
+        # so a sequence drawn twice in one batch writes one value.
+        gt = torch.Generator(device="cpu").manual_seed(4242 + rank)
+        prio_table = (torch.rand(4, replay.num_sequences, generator=gt)
+                      + 0.1).to(device)
         torch.cuda.synchronize()
         batches = None
     else:
@@ -184,6 +231,7 @@ def main():
                    for i in range(args.batches)]
 
     pending = [None]
+    last = [None]   # (loss, priorities) of the most recent step
 
     def one_step(i):
         if replay is not None:
@@ -193,10 +241,14 @@ def main():
             batch = pending[0] if pending[0] is not None else replay.sample()
             tok = replay.sample_async()
             loss, prio = learner.train_step(batch)
-            replay.update_priorities(batch.idxes, prio, batch.old_ptr)
+            replay.update_priorities(
+                batch.idxes,
+                prio_table[i % len(prio_table)].index_select(0, batch.idxes),
+                batch.old_ptr)
             pending[0] = replay.sample_wait(tok)
         else:
-            loss, _ = learner.train_step(batches[i % len(batches)])
+            loss, prio = learner.train_step(batches[i % len(batches)])
+        last[0] = (loss, prio)
         return loss
 
     def barrier():
@@ -235,6 +287,9 @@ def main():
             print(f"  [stage] {name:12s} "
                   f"{ms / (args.warmup + args.steps):8.3f} ms/step",
                   file=sys.stderr)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last[0])
 
     ms_per_step = elapsed / args.steps * 1000.0
     n_gpus = world_size if world_size > 1 else args.gpus

@@ -77,13 +77,18 @@ def test_torchrun_multirank_bench_path():
     import sys
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        # two ranks share the one GPU: RCCL refuses duplicate devices, so
+        # bench.py's documented gloo switch carries the collectives
+        env["R2D2_DIST_BACKEND"] = "gloo"
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
          "--steps", "2", "--warmup", "1", "--batches", "1",
          "--preset", "cartpole"],
-        cwd=repo, capture_output=True, text=True, timeout=240)
+        cwd=repo, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert line, out.stdout
