@@ -152,6 +152,21 @@ PRESETS = {
         game_name="Seaquest", env_type="synthetic", obs_shape=(4, 84, 84),
         action_dim=18, encoder="impala",
     ),
+    # beside the BASELINE five: the reference project's own observation
+    # setup — ONE 84x84 grayscale frame per step, memory left to the LSTM —
+    # so reference-trained checkpoints (1-input-channel conv1) run on the
+    # HIP engine.  Otherwise as `mspacman`.  loss_fn stays at the project
+    # default (huber); the reference trained with MSE (loss_fn="mse").
+    "mspacman_reference": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(1, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=False,
+    ),
+    # the same single-frame setup on `mspacman_gpu_replay`
+    "mspacman_reference_gpu_replay": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(1, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=True, num_actors=256,
+        buffer_capacity=4_000_000, vector_actors=True, actor_device="cuda",
+    ),
 }
 
 

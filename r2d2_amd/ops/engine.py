@@ -33,6 +33,13 @@ PAD_HEAD = 32   # padded output width for the A-dim and V-dim head GEMMs
 KPAD = 32       # LSTM input features padded to a multiple of 32
 
 
+def conv1_channels(encoder):
+    """Input-channel counts the first-layer kernels are instantiated for:
+    the nature conv1 takes a 4-frame stack or the reference's single frame,
+    the IMPALA kernels a 4-frame stack only."""
+    return (1, 4) if encoder == "nature" else (4,)
+
+
 def _round_up(x, m):
     return (x + m - 1) // m * m
 
@@ -266,8 +273,9 @@ class HipNetworkEngine:
             "HIP engine supports the nature/impala 512-hidden configs"
         assert tuple(c.obs_shape[1:]) == (84, 84)
         self.C = c.obs_shape[0]
-        assert self.C == 4, "conv1 kernel instantiated for 4 input channels"
         self.impala = c.encoder == "impala"
+        assert self.C in conv1_channels(c.encoder), \
+            "conv1 kernels instantiated for 1 (nature only) or 4 input channels"
         self.A = c.action_dim
         self.H = 512
         self.device = torch.device(device)
@@ -720,6 +728,10 @@ class HipNetworkEngine:
         # per-image band variant (the 8x8 s4 patch field re-reads only 4x,
         # and the band's whole-image slab costs more occupancy than the
         # dequant re-reads save; conv2/conv3 with 9x/4x re-read DO win).
+        # One input channel (K = 64), same 5440 images: 0.242 ms chunked vs
+        # 0.241 ms band — a tie inside the chunked kernel's own round-to-
+        # round spread (0.2414-0.2444), so both channel counts share the
+        # chunked path.
         dW1, db1 = m.conv_wgrad(d_a1.view(M * 400, 32), a1, obs_hwc, 1,
                                 M, 84, 84, 20, 20, 32, 8 * 8 * self.C)
         self._mark("conv_bwd")
@@ -755,7 +767,8 @@ class HipInference:
     def __init__(self, net, device, config=None):
         c = config or cfg.get()
         assert c.encoder in ("nature", "impala") and c.hidden_dim == 512
-        assert tuple(c.obs_shape) == (4, 84, 84)
+        assert (tuple(c.obs_shape[1:]) == (84, 84)
+                and c.obs_shape[0] in conv1_channels(c.encoder)), c.obs_shape
         self.cfg = c
         self.A = net.action_dim
         self.device = torch.device(device)
@@ -769,7 +782,8 @@ class HipInference:
 
     @torch.no_grad()
     def forward(self, obs_u8_nchw, last_action, last_reward, hidden):
-        """obs: (E, 4, 84, 84) u8 on device; hidden: (h, c) each (1, E, 512)
+        """obs: (E, C, 84, 84) u8 on device, C = the config's obs_shape[0]
+        (4, or 1 for the nature encoder); hidden: (h, c) each (1, E, 512)
         f32.  Returns (q (E, A) f32, (h', c'))."""
         m = self.m
         E = obs_u8_nchw.shape[0]

@@ -46,18 +46,64 @@ __device__ __forceinline__ bf16x8 czero() {
     return r.v;
 }
 
-// load 8 uint8 bytes and dequantize to bf16/255
-__device__ __forceinline__ bf16x8 load_dequant8(const unsigned char* p) {
-    uint2 raw = *reinterpret_cast<const uint2*>(p);
+// dequantize 8 uint8 bytes (two little-endian dwords) to bf16/255
+__device__ __forceinline__ bf16x8 dequant8(unsigned lo, unsigned hi) {
     bf16x8 r;
     const float inv = 1.f / 255.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        r[i] = (__bf16)(((raw.x >> (8 * i)) & 0xff) * inv);
+        r[i] = (__bf16)(((lo >> (8 * i)) & 0xff) * inv);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        r[4 + i] = (__bf16)(((raw.y >> (8 * i)) & 0xff) * inv);
+        r[4 + i] = (__bf16)(((hi >> (8 * i)) & 0xff) * inv);
     return r;
+}
+
+// load 8 uint8 bytes (8-byte aligned) and dequantize to bf16/255
+__device__ __forceinline__ bf16x8 load_dequant8(const unsigned char* p) {
+    uint2 raw = *reinterpret_cast<const uint2*>(p);
+    return dequant8(raw.x, raw.y);
+}
+
+// ---------------------------------------------------------------------------
+// Patch-row loads, selected on CIN.  A lane's 8 k-elements are one
+// contiguous run of the NHWC image starting at element
+//   ((n*INH + oy*S + dy)*INW + ox*S)*CIN + rem.
+// CIN == 4 (frame stack): ox*S*CIN = 16*ox and INW*CIN = 336 = 16*21, so the
+// run is 16-byte aligned in u8 and in bf16 — one 8-byte global load, one
+// 16-byte LDS read.
+// CIN == 1 (single frame): the run starts at 4*ox + 84*row elements, i.e.
+// only 4-byte aligned as u8 in global memory and only 8-byte aligned as bf16
+// in LDS.  A wider access through a cast would assert an alignment the
+// address does not have (off-alignment b128 LDS reads replay, and nothing
+// guarantees the compiler splits them), so the access is issued at the
+// alignment it really has: two 4-byte global loads, two 8-byte LDS reads.
+// Restaging the image so the wide read is aligned would need a second,
+// 4-element-shifted LDS copy for odd ox; K is only 64 here, the split read
+// is the simpler choice.  Whole-image staging stays on the wide helpers:
+// 84*84 = 8*882 bytes per image keeps every image base 8-byte aligned.
+// ---------------------------------------------------------------------------
+template <int CIN>
+__device__ __forceinline__ bf16x8 load_patch_u8(const unsigned char* p) {
+    if constexpr (CIN == 1) {
+        const unsigned* q = reinterpret_cast<const unsigned*>(p);
+        return dequant8(q[0], q[1]);
+    } else {
+        return load_dequant8(p);
+    }
+}
+
+template <int CIN>
+__device__ __forceinline__ bf16x8 lds_patch_row(const __hip_bfloat16* p) {
+    if constexpr (CIN == 1) {
+        const uint2* q = reinterpret_cast<const uint2*>(p);
+        uint2 lo = q[0], hi = q[1];
+        cbf8u r;
+        r.u = uint4{lo.x, lo.y, hi.x, hi.y};
+        return r.v;
+    } else {
+        return *reinterpret_cast<const bf16x8*>(p);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -115,7 +161,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(
         for (int i = 0; i < 2; ++i) {
             if (avalid[i]) {
                 if (IN_U8)
-                    a[i] = load_dequant8(
+                    a[i] = load_patch_u8<CIN>(
                         reinterpret_cast<const unsigned char*>(in) + abase[i] + off);
                 else
                     a[i] = cload_bf16x8(
@@ -377,7 +423,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     // NCOT = co tiles of 32 (1 when COUT<=32): waves split K 4/NCOT ways so
     // no wave computes guarded-away co columns
     constexpr int NKW = 4 / NCOT;                     // k splits
-    constexpr int KHALF = ((K / NKW + 31) / 32) * 32; // per-wave k extent
+    // per-wave k extent, in whole 16-col fragments (K = 64, the one-channel
+    // conv1, gives each of the 4 waves exactly one fragment)
+    constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
     constexpr int KFRAG = KHALF / 16;                 // 16-col frags per wave
     __shared__ __hip_bfloat16 s_dy[32][64 + 8];
     __shared__ __hip_bfloat16 s_a[32][K + 8];
@@ -431,7 +479,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
                     int dy_ = k / KWC, rem = k % KWC;
                     long off = base + (long)dy_ * INW * CIN + rem;
                     if (IN_U8)
-                        w = load_dequant8(
+                        w = load_patch_u8<CIN>(
                             reinterpret_cast<const unsigned char*>(in) + off);
                     else
                         w = cload_bf16x8(
@@ -581,8 +629,7 @@ __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
                     a[i] = pval[i]
-                        ? *reinterpret_cast<const bf16x8*>(
-                              &s_img[pbase[i] + off])
+                        ? lds_patch_row<CIN>(&s_img[pbase[i] + off])
                         : czero();
 #pragma unroll
                 for (int j = 0; j < NB; ++j)
@@ -639,7 +686,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
     constexpr int NPIX = OH * OW;
     constexpr int NCOT = (COUT_T + 31) / 32;          // cout tiles of 32
     constexpr int NKW = 4 / NCOT;                     // k splits
-    constexpr int KHALF = ((K / NKW + 31) / 32) * 32;
+    constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
     constexpr int KFRAG = KHALF / 16;
 
     __shared__ __hip_bfloat16 s_img[INH * INW * CIN];
@@ -705,7 +752,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
                     if (pp < NPIX) {
                         int oy = pp / OW, ox = pp % OW;
                         int dy_ = k / KWC, rem = k % KWC;
-                        w = *reinterpret_cast<const bf16x8*>(
+                        w = lds_patch_row<CIN>(
                             &s_img[((oy * S + dy_) * INW + ox * S) * CIN + rem]);
                     }
                     *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
@@ -772,7 +819,37 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
 
 static inline int ccdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// conv_id: 1 = 8x8 s4 CIN variable(4) u8-in, 2 = 4x4 s2 CIN 32, 3 = 3x3 s1 CIN 64
+// conv1 input guard.  The kernels index the frames as a dense (N, INH, INW,
+// CIN) u8 array and load them `wide` bytes at a time from data_ptr, so a
+// strided view or a base pointer off that alignment must raise here, before
+// any launch.  Returns CIN (1 = single frame, 4 = frame stack); `wide1` /
+// `wide4` are the widest global load the chosen kernel issues per variant.
+static int conv1_cin(const torch::Tensor& in, int64_t N, int64_t INH,
+                     int64_t INW, int wide1, int wide4, const char* who) {
+    TORCH_CHECK(in.is_cuda() && in.dtype() == torch::kUInt8, who,
+                ": conv1 input must be a uint8 device tensor");
+    TORCH_CHECK(in.dim() == 4 && in.size(0) == N && in.size(1) == INH
+                && in.size(2) == INW, who,
+                ": conv1 input must be (N, H, W, C) = (", N, ", ", INH, ", ",
+                INW, ", C), got ", in.sizes());
+    int64_t C = in.size(3);
+    TORCH_CHECK(C == 1 || C == 4, who,
+                ": conv1 is instantiated for 1 or 4 input channels, got ", C);
+    TORCH_CHECK(in.is_contiguous(), who, ": conv1 input must be contiguous");
+    int wide = (C == 1) ? wide1 : wide4;
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(in.data_ptr()) % wide == 0, who,
+                ": conv1 input data_ptr must be ", wide, "-byte aligned");
+    return (int)C;
+}
+
+static void conv1_wt_check(const torch::Tensor& Wt, int cin, const char* who) {
+    TORCH_CHECK(Wt.dim() == 2 && Wt.size(0) == 32 && Wt.size(1) == 64 * cin,
+                who, ": conv1 weights must be (32, ", 64 * cin, "), got ",
+                Wt.sizes());
+}
+
+// conv_id: 1 = 8x8 s4 u8-in, CIN 1 or 4 (taken from in.size(3)),
+//          2 = 4x4 s2 CIN 32, 3 = 3x3 s1 CIN 64
 torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
                        int64_t conv_id, int64_t N, int64_t INH, int64_t INW,
                        int64_t OH, int64_t OW, bool relu) {
@@ -791,11 +868,17 @@ torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
                        grid,                                                   \
                        dim3(256), 0, stream.stream(), x, w, b, o, (int)M,      \
                        (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT)
+#define C1LAUNCH(CIN_)                                                         \
+    hipLaunchKernelGGL((conv_fwd_kernel<true, 8, 8, CIN_, 4, 32, true>), grid, \
+                       dim3(256), 0, stream.stream(), x, w, b, o, (int)M,      \
+                       (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT)
     if (conv_id == 1) {
-        TORCH_CHECK(in.dtype() == torch::kUInt8);
-        hipLaunchKernelGGL((conv_fwd_kernel<true, 8, 8, 4, 4, 32, true>), grid,
-                           dim3(256), 0, stream.stream(), x, w, b, o, (int)M,
-                           (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT);
+        TORCH_CHECK((OH - 1) * 4 + 8 <= INH && (OW - 1) * 4 + 8 <= INW,
+                    "conv_fwd: conv1 output extent exceeds the input");
+        int cin = conv1_cin(in, N, INH, INW, 4, 8, "conv_fwd");
+        conv1_wt_check(Wt, cin, "conv_fwd");
+        if (cin == 1) C1LAUNCH(1);
+        else C1LAUNCH(4);
     } else if (conv_id == 2) {
         TORCH_CHECK(in.dtype() == torch::kBFloat16);
         CLAUNCH(false, 4, 4, 32, 2);
@@ -804,6 +887,7 @@ torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
     } else {
         TORCH_CHECK(false, "unknown conv_id");
     }
+#undef C1LAUNCH
 #undef CLAUNCH
     return out;
 }
@@ -912,7 +996,11 @@ torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
                        dim3(grid), dim3(256), 0, stream.stream(), x, w, b, o,  \
                        (int)N, imgs, CO0_)
     if (conv_id == 1) {
-        FBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32, 0);
+        // whole-image staging loads 8 bytes per lane for both variants
+        int cin = conv1_cin(in, N, 84, 84, 8, 8, "conv_fwd_band");
+        conv1_wt_check(Wt, cin, "conv_fwd_band");
+        if (cin == 1) FBLAUNCH(true, 8, 8, 1, 4, 84, 20, 32, 0);
+        else FBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32, 0);
     } else if (conv_id == 2) {   // 64-out: two 32-col launches (LDS halved)
         FBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64, 0);
         FBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64, 32);
@@ -932,8 +1020,14 @@ std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
                                            torch::Tensor in, int64_t conv_id,
                                            int64_t N) {
     long COUT = (conv_id == 1) ? 32 : 64;
-    long K = (conv_id == 1) ? 8 * 8 * 4 : (conv_id == 2) ? 4 * 4 * 32
-                                                         : 3 * 3 * 64;
+    // whole-image staging loads 8 bytes per lane for both conv1 variants
+    int cin1 = (conv_id == 1)
+        ? conv1_cin(in, N, 84, 84, 8, 8, "conv_wgrad_band") : 0;
+    long K = (conv_id == 1) ? 8 * 8 * cin1 : (conv_id == 2) ? 4 * 4 * 32
+                                                            : 3 * 3 * 64;
+    if (conv_id == 1)
+        TORCH_CHECK(dY.numel() == N * 400 * 32 && act.numel() == dY.numel(),
+                    "conv_wgrad_band: conv1 dY/act must be (N*400, 32)");
     auto dWt = torch::zeros({COUT, K}, dY.options().dtype(torch::kFloat32));
     auto db = torch::zeros({COUT}, dY.options().dtype(torch::kFloat32));
     int imgs = (int)((N + 1023) / 1024);
@@ -948,7 +1042,8 @@ std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
                        dim3(grid), dim3(256), 0, stream.stream(), dy, ac, x,   \
                        dWt.data_ptr<float>(), db.data_ptr<float>(), (int)N,    \
                        imgs)
-    if (conv_id == 1) WBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32);
+    if (conv_id == 1 && cin1 == 1) WBLAUNCH(true, 8, 8, 1, 4, 84, 20, 32);
+    else if (conv_id == 1) WBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32);
     else if (conv_id == 2) WBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64);
     else if (conv_id == 3) WBLAUNCH(false, 3, 3, 64, 1, 9, 7, 64);
     else TORCH_CHECK(false, "unknown conv_id");
@@ -962,6 +1057,17 @@ std::vector<torch::Tensor> conv_wgrad(torch::Tensor dY, torch::Tensor act,
                                       int64_t OH, int64_t OW, int64_t COUT,
                                       int64_t K) {
     long M = N * OH * OW;
+    int cin1 = 0;
+    if (conv_id == 1) {
+        TORCH_CHECK((OH - 1) * 4 + 8 <= INH && (OW - 1) * 4 + 8 <= INW,
+                    "conv_wgrad: conv1 output extent exceeds the input");
+        cin1 = conv1_cin(in, N, INH, INW, 4, 8, "conv_wgrad");
+        TORCH_CHECK(K == 64 * cin1 && COUT == 32,
+                    "conv_wgrad: conv1 expects COUT 32 and K = 64 * CIN = ",
+                    64 * cin1, ", got COUT ", COUT, " K ", K);
+        TORCH_CHECK(dY.numel() == M * COUT && act.numel() == dY.numel(),
+                    "conv_wgrad: conv1 dY/act must be (N*OH*OW, 32)");
+    }
     auto dWt = torch::zeros({COUT, K}, dY.options().dtype(torch::kFloat32));
     auto db = torch::zeros({COUT}, dY.options().dtype(torch::kFloat32));
     long target_chunks = 1024;
@@ -979,7 +1085,8 @@ std::vector<torch::Tensor> conv_wgrad(torch::Tensor dY, torch::Tensor act,
                        dWt.data_ptr<float>(), db.data_ptr<float>(), (int)M,    \
                        (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT,        \
                        (int)rows_per_chunk)
-    if (conv_id == 1) WLAUNCH(true, 8, 8, 4, 4, 1);
+    if (conv_id == 1 && cin1 == 1) WLAUNCH(true, 8, 8, 1, 4, 1);
+    else if (conv_id == 1) WLAUNCH(true, 8, 8, 4, 4, 1);
     else if (conv_id == 2) WLAUNCH(false, 4, 4, 32, 2, 2);
     else if (conv_id == 3) WLAUNCH(false, 3, 3, 64, 1, 2);
     else TORCH_CHECK(false, "unknown conv_id");

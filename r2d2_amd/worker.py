@@ -702,8 +702,10 @@ class Learner:
         hip_ops.ext(required=True)
         self.hip_engine = True
         c = self.cfg
+        from .ops.engine import conv1_channels
         if (c.encoder in ("nature", "impala") and c.hidden_dim == 512
-                and len(c.obs_shape) == 3 and c.obs_shape[0] == 4
+                and len(c.obs_shape) == 3
+                and c.obs_shape[0] in conv1_channels(c.encoder)
                 and self.device.type == "cuda"):
             from .ops.engine import HipNetworkEngine
             self.engine = HipNetworkEngine(self.online_net, self.target_net,
@@ -1217,9 +1219,11 @@ class VectorActor:
         self.hip_inf = None
         self.weight_bus = weight_bus
         self._bus_ver = 0
+        from .ops.engine import conv1_channels
         if (self.device.type == "cuda" and c.use_hip_kernels
                 and c.encoder in ("nature", "impala") and c.hidden_dim == 512
-                and tuple(c.obs_shape) == (4, 84, 84)):
+                and tuple(c.obs_shape[1:]) == (84, 84)
+                and c.obs_shape[0] in conv1_channels(c.encoder)):
             from .ops.engine import HipInference
             self.hip_inf = HipInference(self.model, self.device)
             if self.weight_bus is not None:   # catch up if already published
