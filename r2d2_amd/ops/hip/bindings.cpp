@@ -53,11 +53,6 @@ void gemm_wgrad_into(torch::Tensor dY, torch::Tensor act_out, torch::Tensor A,
 torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
                        int64_t conv_id, int64_t N, int64_t INH, int64_t INW,
                        int64_t OH, int64_t OW, bool relu);
-torch::Tensor conv_dgrad(torch::Tensor dYp, torch::Tensor Wd, torch::Tensor taps,
-                         int64_t N, int64_t PH, int64_t PW, int64_t COUT,
-                         int64_t XH, int64_t XW, int64_t CIN,
-                         int64_t y0, int64_t x0, int64_t S, int64_t pad,
-                         torch::Tensor dX);
 torch::Tensor conv_dgrad_dense(torch::Tensor dY, torch::Tensor Wd,
                                torch::Tensor taps, torch::Tensor actx,
                                int64_t N, int64_t OH, int64_t OW, int64_t COUT,
@@ -161,7 +156,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("db_out"), pybind11::arg("kd0") = 0,
           pybind11::arg("kd1") = 0, pybind11::arg("kd2") = 0);
     m.def("conv_fwd", &conv_fwd, "Implicit-GEMM MFMA conv forward (NHWC)");
-    m.def("conv_dgrad", &conv_dgrad, "MFMA conv backward-data (tap classes)");
     m.def("conv_dgrad_dense", &conv_dgrad_dense,
           "MFMA conv backward-data from dense pre-masked dY (bounds-checked "
           "taps, optional fused output ReLU mask)");

@@ -9,6 +9,34 @@
 #define WAVE 64
 
 // ---------------------------------------------------------------------------
+// MFMA operand vectors: 8 bf16 = one 16-byte A/B fragment per lane, 4 f32 =
+// one 16x16 accumulator fragment.  Fragments move as a single 16-byte access.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+union bf16x8_u {
+    bf16x8 v;
+    uint4 u;
+    __bf16 e[8];
+};
+
+__device__ __forceinline__ bf16x8 load_bf16x8(const __hip_bfloat16* p) {
+    bf16x8_u r;
+    r.u = *reinterpret_cast<const uint4*>(p);
+    return r.v;
+}
+
+__device__ __forceinline__ bf16x8 zero_bf16x8() {
+    bf16x8_u r;
+    r.u = uint4{0, 0, 0, 0};
+    return r.v;
+}
+
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---------------------------------------------------------------------------
 // R2D2 value rescaling h(x) = sign(x)(sqrt(|x|+1)-1) + eps*x and its inverse
 // (golden: r2d2_amd/ops/functional.py; reference semantics worker.py:383-390)
 // ---------------------------------------------------------------------------
@@ -61,18 +89,15 @@ __device__ __forceinline__ float wave_allreduce_max(float v) {
 // (tools/tr16_probe.hip -> gpurun_out/tr16_semantics.log mode 1).
 // Requires col0 % 4 == 0 and the 16-column span in-bounds.
 // ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) __bf16 cmn_bf16x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 cmn_bf16x8;
-
 template <int LDE>
-__device__ __forceinline__ cmn_bf16x8 lds_col_frag8(
+__device__ __forceinline__ bf16x8 lds_col_frag8(
     const __hip_bfloat16* s, int row0, int col0, int lane) {
     int i15 = lane & 15;
-    auto* p = (__attribute__((address_space(3))) cmn_bf16x4*)
+    auto* p = (__attribute__((address_space(3))) bf16x4*)
         (s + (row0 + (i15 >> 2)) * LDE + col0 + 4 * (i15 & 3));
     union {
-        struct { cmn_bf16x4 lo, hi; } p2;
-        cmn_bf16x8 v;
+        struct { bf16x4 lo, hi; } p2;
+        bf16x8 v;
     } u;
     u.p2.lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);      // rows 0..3
     u.p2.hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p + LDE); // rows 4..7

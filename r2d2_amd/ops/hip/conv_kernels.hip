@@ -11,40 +11,26 @@
 // global, no im2col materialization.  Weights are prepacked (COUT, K) for
 // forward / wgrad and (CIN, TAPS*COUT) per tap-class for dgrad.
 //
-// Forward:  out(M=N*OH*OW, COUT) = act(patch(M,K) @ Wt^T + bias)
-// Dgrad:    dX from a zero-padded dY via uniform tap tables (stride-2 convs
-//           split into parity classes so every row in a tile has the same
-//           taps; no divergence).
+// Structure: the three layers are described once, as types (Conv1<CIN>,
+// Conv2, Conv3); every kernel takes one of them as its only geometry
+// parameter and the host dispatcher (dispatch_layer) maps (conv_id, cin) to
+// it.  Nothing else is instantiated: a call that matches no layer raises.
+//
+// Forward:  out(M=N*OH*OW, COUT) = act(patch(M,K) @ Wt^T + bias); classic
+//           (global patch reads) and band (whole image + weights in LDS).
+// Dgrad:    dX from the dense, pre-masked dY via uniform tap tables
+//           (stride-2 convs split into parity classes so every row in a
+//           tile has the same taps; no divergence); out-of-range taps are
+//           dropped by a bounds check.
 // Wgrad:    dWt(COUT,K) += dY^T @ patch with LDS-staged 32-row tiles and
-//           f32 atomics; fused ReLU mask + bias grad.
+//           f32 atomics; fused ReLU mask + bias grad; chunked (global patch
+//           reads) and band (whole image in LDS).  Both run WgradTile.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
 #include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-union cbf8u {
-    bf16x8 v;
-    uint4 u;
-    __bf16 e[8];
-    unsigned short s[8];
-};
-
-__device__ __forceinline__ bf16x8 cload_bf16x8(const __hip_bfloat16* p) {
-    cbf8u r;
-    r.u = *reinterpret_cast<const uint4*>(p);
-    return r.v;
-}
-
-__device__ __forceinline__ bf16x8 czero() {
-    cbf8u r;
-    r.u = uint4{0, 0, 0, 0};
-    return r.v;
-}
 
 // dequantize 8 uint8 bytes (two little-endian dwords) to bf16/255
 __device__ __forceinline__ bf16x8 dequant8(unsigned lo, unsigned hi) {
@@ -98,7 +84,7 @@ __device__ __forceinline__ bf16x8 lds_patch_row(const __hip_bfloat16* p) {
     if constexpr (CIN == 1) {
         const uint2* q = reinterpret_cast<const uint2*>(p);
         uint2 lo = q[0], hi = q[1];
-        cbf8u r;
+        bf16x8_u r;
         r.u = uint4{lo.x, lo.y, hi.x, hi.y};
         return r.v;
     } else {
@@ -107,70 +93,166 @@ __device__ __forceinline__ bf16x8 lds_patch_row(const __hip_bfloat16* p) {
 }
 
 // ---------------------------------------------------------------------------
+// Layer geometry, stated once.  Square or not, everything a kernel or a host
+// check needs derives from these eight facts per layer.
+// ---------------------------------------------------------------------------
+template <int KH_, int KW_, int CIN_, int S_, int INH_, int INW_, int COUT_,
+          bool IN_U8_>
+struct ConvGeom {
+    static constexpr int KH = KH_, KW = KW_, CIN = CIN_, S = S_;
+    static constexpr int INH = INH_, INW = INW_, COUT = COUT_;
+    static constexpr bool IN_U8 = IN_U8_;       // u8 input, fused /255
+    static constexpr int OH = (INH - KH) / S + 1;
+    static constexpr int OW = (INW - KW) / S + 1;
+    static constexpr int K = KH * KW * CIN;     // GEMM reduction extent
+    static constexpr int KWC = KW * CIN;        // one kernel row (contiguous)
+    static constexpr int NPIX = OH * OW;        // output pixels per image
+    static constexpr int IMG = INH * INW * CIN; // input elements per image
+    // dgrad: taps per stride-parity class, and that class's dX grid.  For
+    // every layer S | INH, so the grid is the same for every parity offset.
+    static constexpr int TAPS = (KH / S) * (KW / S);
+    static constexpr int CLS_H = INH / S, CLS_W = INW / S;
+    static_assert(KWC % 8 == 0 && K % 32 == 0 && IMG % 8 == 0,
+                  "8-element lane runs / 32-wide MFMA k-tiles");
+    static_assert(KH % S == 0 && KW % S == 0 && INH % S == 0 && INW % S == 0,
+                  "uniform dgrad parity classes");
+};
+
+// conv1: 8x8 s4 over the 84x84 u8 frames, CIN 1 (single frame) or 4 (stack);
+// conv2: 4x4 s2; conv3: 3x3 s1.  Each layer's input is the one below's output.
+template <int CIN>
+using Conv1 = ConvGeom<8, 8, CIN, 4, 84, 84, 32, true>;
+using Conv2 = ConvGeom<4, 4, Conv1<4>::COUT, 2, Conv1<4>::OH, Conv1<4>::OW,
+                       64, false>;
+using Conv3 = ConvGeom<3, 3, Conv2::COUT, 1, Conv2::OH, Conv2::OW, 64, false>;
+
+// ---------------------------------------------------------------------------
+// Shared device pieces
+// ---------------------------------------------------------------------------
+
+// Warp-tile coordinates of a 256-thread workgroup, each wave a 32x32 tile of
+// 2x2 MFMA fragments.  NCOL == 32 (e.g. conv1 COUT=32): the 4 waves stack on
+// the M dim (128 rows) so no wave computes guarded-away columns; else the
+// classic 2x2 (64 rows x 64 cols).
+template <int NOUT>
+constexpr int tile_ncol = NOUT <= 32 ? 32 : 64;
+
+template <int NCOL>
+struct WarpTile {
+    static constexpr int ROWS = NCOL == 32 ? 128 : 64;
+    int lane, wr, wc;
+    int frow;   // fragment row/col this lane loads
+    int kseg;   // its 8-element k segment within a 32-wide k-tile
+    __device__ __forceinline__ WarpTile() {
+        int wave = threadIdx.x / WAVE;
+        lane = threadIdx.x & (WAVE - 1);
+        wr = (NCOL == 32) ? wave : (wave >> 1);
+        wc = (NCOL == 32) ? 0 : (wave & 1);
+        frow = lane & 15;
+        kseg = (lane >> 4) * 8;
+    }
+    __device__ __forceinline__ long row0() const {
+        return (long)blockIdx.x * ROWS + wr * 32;
+    }
+    __device__ __forceinline__ long col0() const {
+        return (long)blockIdx.y * 64 + wc * 32;
+    }
+};
+
+// Walk a wave's MFMA accumulators: acc[i][j] is the 16x16 fragment at
+// (16*i, 16*j) of the wave tile, of which a lane holds column lane&15, rows
+// 4*(lane>>4) .. +3.  Calls f(row, col, value) with tile-relative coordinates.
+template <int NI, int NJ, class F>
+__device__ __forceinline__ void for_each_acc(const f32x4 (&acc)[NI][NJ],
+                                             int lane, F&& f) {
+    int ccol = lane & 15;
+    int crow = (lane >> 4) * 4;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                f(i * 16 + crow + r, j * 16 + ccol, acc[i][j][r]);
+}
+
+// Element offset of the patch origin of GEMM row r = (n, oy, ox).
+// 32-bit index math: M <= B*T*84*84 < 2^31, and the divisors are constants,
+// so the divisions lower to multiply-shift.
+template <class G>
+__device__ __forceinline__ long patch_origin(unsigned r) {
+    unsigned n = r / (unsigned)G::NPIX;
+    unsigned p = r % (unsigned)G::NPIX;
+    int oy = p / (unsigned)G::OW, ox = p % (unsigned)G::OW;
+    return (((long)n * G::INH + (long)oy * G::S) * G::INW + (long)ox * G::S)
+           * G::CIN;
+}
+
+// 8 k-elements of a patch row from the global image, at element offset off
+template <class G>
+__device__ __forceinline__ bf16x8 load_patch_row(const void* in, long off) {
+    if constexpr (G::IN_U8)
+        return load_patch_u8<G::CIN>(
+            reinterpret_cast<const unsigned char*>(in) + off);
+    else
+        return load_bf16x8(reinterpret_cast<const __hip_bfloat16*>(in) + off);
+}
+
+// Stage image n whole into LDS (one global read + one dequant per element).
+// The caller owns the barriers around it.
+template <class G>
+__device__ __forceinline__ void stage_image(__hip_bfloat16* s_img,
+                                            const void* in, long n) {
+    const long gbase = n * G::IMG;
+    for (int e = threadIdx.x * 8; e < G::IMG; e += blockDim.x * 8) {
+        bf16x8 v;
+        if constexpr (G::IN_U8)
+            v = load_dequant8(
+                reinterpret_cast<const unsigned char*>(in) + gbase + e);
+        else
+            v = load_bf16x8(
+                reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
+        *reinterpret_cast<bf16x8*>(&s_img[e]) = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Forward
 // ---------------------------------------------------------------------------
-template <bool IN_U8, int KH, int KW, int CIN, int S, int NCOL, bool RELU>
+template <class G, bool RELU>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(
     const void* __restrict__ in,            // (N, INH, INW, CIN)
     const __hip_bfloat16* __restrict__ Wt,  // (COUT, K)
     const float* __restrict__ bias,         // (COUT,)
     __hip_bfloat16* __restrict__ out,       // (M, COUT)
-    int M, int INH, int INW, int OH, int OW, int COUT) {
-    constexpr int K = KH * KW * CIN;
-    constexpr int KWC = KW * CIN;
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    // NCOL == 32 (e.g. conv1 COUT=32): 4 waves stack on the M dim so no
-    // wave computes guarded-away columns; else classic 2x2
-    int wr = (NCOL == 32) ? wave : (wave >> 1);
-    int wc = (NCOL == 32) ? 0 : (wave & 1);
-    long row0 = (long)blockIdx.x * (NCOL == 32 ? 128 : 64) + wr * 32;
-    long col0 = (long)blockIdx.y * 64 + wc * 32;
-    int frow = lane & 15;
-    int kseg = (lane >> 4) * 8;
+    int M) {
+    constexpr int K = G::K, COUT = G::COUT;
+    const WarpTile<tile_ncol<COUT>> wt;
+    const long row0 = wt.row0(), col0 = wt.col0();
 
     // per-lane patch base addresses for its two A rows
-    // 32-bit index math: M <= B*T*84*84 < 2^31, so unsigned division
-    // lowers to multiply-shift instead of 64-bit libcalls
-    const unsigned OHW = (unsigned)(OH * OW);
     long abase[2];
     bool avalid[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        unsigned r = (unsigned)row0 + i * 16 + frow;
+        unsigned r = (unsigned)row0 + i * 16 + wt.frow;
         avalid[i] = r < (unsigned)M;
-        if (avalid[i]) {
-            unsigned n = r / OHW;
-            unsigned p = r % OHW;
-            int oy = p / (unsigned)OW, ox = p % (unsigned)OW;
-            abase[i] = (((long)n * INH + (long)oy * S) * INW
-                        + (long)ox * S) * CIN;
-        } else {
-            abase[i] = 0;
-        }
+        abase[i] = avalid[i] ? patch_origin<G>(r) : 0;
     }
 
     f32x4 acc[2][2] = {};
     for (int k0 = 0; k0 < K; k0 += 32) {
-        int k = k0 + kseg;
-        int dy = k / KWC;
-        int rem = k % KWC;
-        long off = (long)dy * INW * CIN + rem;
+        int k = k0 + wt.kseg;
+        int dy = k / G::KWC;
+        int rem = k % G::KWC;
+        long off = (long)dy * G::INW * G::CIN + rem;
         bf16x8 a[2], b[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (avalid[i]) {
-                if (IN_U8)
-                    a[i] = load_patch_u8<CIN>(
-                        reinterpret_cast<const unsigned char*>(in) + abase[i] + off);
-                else
-                    a[i] = cload_bf16x8(
-                        reinterpret_cast<const __hip_bfloat16*>(in) + abase[i] + off);
-            } else {
-                a[i] = czero();
-            }
-            long c = col0 + i * 16 + frow;
-            b[i] = (c < COUT) ? cload_bf16x8(Wt + c * K + k0 + kseg) : czero();
+            a[i] = avalid[i] ? load_patch_row<G>(in, abase[i] + off)
+                             : zero_bf16x8();
+            long c = col0 + i * 16 + wt.frow;
+            b[i] = (c < COUT) ? load_bf16x8(Wt + c * K + k) : zero_bf16x8();
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -180,179 +262,71 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(
                     a[i], b[j], acc[i][j], 0, 0, 0);
     }
 
-    int ccol = lane & 15;
-    int crow = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long rr = row0 + i * 16 + crow + r;
-                long cc = col0 + j * 16 + ccol;
-                if (rr < M && cc < COUT) {
-                    float v = acc[i][j][r] + bias[cc];
-                    if (RELU) v = fmaxf(v, 0.f);
-                    out[rr * COUT + cc] = f2bf(v);
-                }
-            }
-}
-
-// ---------------------------------------------------------------------------
-// Dgrad: dX[n, y, x, ci] = sum_t sum_co dYp[n, (y-dy_t)/S + pad, ...] *
-//                          Wd[ci][t*COUT + co]
-// Launched per tap-class; rows enumerate the class's (n, yy, xx) grid with
-// y = y0 + yy*S.  dYp is the zero-PADDED upstream gradient (pre-masked by
-// the ReLU of this conv's output).
-// ---------------------------------------------------------------------------
-// CO_T: compile-time COUT (both nature dgrads have COUT=64) — the k ->
-// (tap, co) split per lane per k-iteration otherwise runs runtime
-// divisions (PMC: 72:1 VALU:MFMA on this kernel).
-template <int TAPS, int NCOL, int CO_T = 0>
-__global__ __launch_bounds__(256) void conv_dgrad_kernel(
-    const __hip_bfloat16* __restrict__ dYp,  // (N, PH, PW, COUT)
-    const __hip_bfloat16* __restrict__ Wd,   // (CIN, TAPS*COUT)
-    __hip_bfloat16* __restrict__ dX,         // (N, XH, XW, CIN)
-    const int* __restrict__ taps,            // (TAPS, 2): dy, dx
-    int Mc, int YY, int XX, int y0, int x0, int S, int pad,
-    int PH, int PW, int COUT, int XH, int XW, int CIN) {
-    const int COUTc = CO_T ? CO_T : COUT;
-    const int K = TAPS * COUTc;
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    int wr = (NCOL == 32) ? wave : (wave >> 1);
-    int wc = (NCOL == 32) ? 0 : (wave & 1);
-    long row0 = (long)blockIdx.x * (NCOL == 32 ? 128 : 64) + wr * 32;
-    long col0 = (long)blockIdx.y * 64 + wc * 32;
-    int frow = lane & 15;
-    int kseg = (lane >> 4) * 8;
-
-    // per-lane (n, y, x) for its two rows (32-bit division)
-    const unsigned YX = (unsigned)(YY * XX);
-    long nbase[2];
-    int yv[2], xv[2];
-    bool avalid[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        unsigned r = (unsigned)row0 + i * 16 + frow;
-        avalid[i] = r < (unsigned)Mc;
-        unsigned n = avalid[i] ? r / YX : 0;
-        unsigned p = avalid[i] ? r % YX : 0;
-        yv[i] = y0 + (int)(p / (unsigned)XX) * S;
-        xv[i] = x0 + (int)(p % (unsigned)XX) * S;
-        nbase[i] = (long)n * PH * PW;
-    }
-
-    f32x4 acc[2][2] = {};
-    for (int k0 = 0; k0 < K; k0 += 32) {
-        int k = k0 + kseg;
-        int t = (unsigned)k / (unsigned)COUTc;
-        int co = (unsigned)k % (unsigned)COUTc;
-        int dy = taps[2 * t], dx = taps[2 * t + 1];
-        bf16x8 a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (avalid[i]) {
-                int oy = (yv[i] - dy) / S + pad;
-                int ox = (xv[i] - dx) / S + pad;
-                a[i] = cload_bf16x8(dYp + (nbase[i] + (long)oy * PW + ox) * COUT + co);
-            } else {
-                a[i] = czero();
-            }
-            long c = col0 + i * 16 + frow;
-            b[i] = (c < CIN) ? cload_bf16x8(Wd + c * K + k0 + kseg) : czero();
+    for_each_acc(acc, wt.lane, [&](int r, int c, float v) {
+        long rr = row0 + r;
+        long cc = col0 + c;
+        if (rr < M && cc < COUT) {
+            v += bias[cc];
+            if (RELU) v = fmaxf(v, 0.f);
+            out[rr * COUT + cc] = f2bf(v);
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-
-    int ccol = lane & 15;
-    int crow = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long rr = row0 + i * 16 + crow + r;
-                long cc = col0 + j * 16 + ccol;
-                if (rr < Mc && cc < CIN) {
-                    unsigned n = (unsigned)rr / YX;
-                    unsigned p = (unsigned)rr % YX;
-                    int y = y0 + (int)(p / (unsigned)XX) * S;
-                    int x = x0 + (int)(p % (unsigned)XX) * S;
-                    dX[(((long)n * XH + y) * XW + x) * CIN + cc] =
-                        f2bf(acc[i][j][r]);
-                }
-            }
+    });
 }
 
 // ---------------------------------------------------------------------------
-// Dgrad from the DENSE (unpadded, pre-masked) upstream gradient
-// dY (N, OH, OW, COUT): taps landing outside [0,OH)x[0,OW) contribute zero
-// via a bounds check instead of a zero-padded staging copy (drops the
-// dyp zeros-fill + interior copy + separate ReLU-mask pass from the engine
-// backward).  OUT_MASK applies the ReLU mask of the conv BELOW
-// ((act_x > 0) at the dX address) on store, so the next layer's dgrad and
-// wgrad consume a pre-masked tensor directly.
+// Dgrad of layer G from the DENSE (unpadded, pre-masked) upstream gradient:
+//   dX[n, y, x, ci] = sum_t sum_co dY[n, (y-dy_t)/S, (x-dx_t)/S, co] *
+//                     Wd[ci][t*COUT + co]
+// Launched per stride-parity class (y0, x0); rows enumerate the class's
+// (n, yy, xx) grid with y = y0 + yy*S, so every row has the same TAPS taps.
+// Taps landing outside [0,OH)x[0,OW) contribute zero via a bounds check
+// instead of a zero-padded staging copy.  OUT_MASK applies the ReLU mask of
+// the conv BELOW ((act_x > 0) at the dX address) on store, so the next
+// layer's dgrad and wgrad consume a pre-masked tensor directly.
+// All geometry is compile-time: the per-lane row->(n,y,x) and k->(tap,co)
+// divisions lower to mul-shift (the kernel is otherwise VALU-bound on
+// address math).
 // ---------------------------------------------------------------------------
-// GT (geometry template): nonzero = compile-time (OH==OW, XH==XW, S) for
-// the hot Nature shapes — the per-lane row->(n,y,x) and tap divisions
-// lower to mul-shift by constants (this kernel is otherwise VALU-bound on
-// address math, r06 PMC 72:1 VALU:MFMA).  Encoded GT = OH*1000 + XH*10 + S.
-template <int TAPS, int NCOL, int CO_T, bool OUT_MASK, int GT = 0>
+template <class G, bool OUT_MASK>
 __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
     const __hip_bfloat16* __restrict__ dY,   // (N, OH, OW, COUT)
     const __hip_bfloat16* __restrict__ Wd,   // (CIN, TAPS*COUT)
-    const __hip_bfloat16* __restrict__ actx, // (N, XH, XW, CIN) or null
-    __hip_bfloat16* __restrict__ dX,         // (N, XH, XW, CIN)
+    const __hip_bfloat16* __restrict__ actx, // (N, INH, INW, CIN) or null
+    __hip_bfloat16* __restrict__ dX,         // (N, INH, INW, CIN)
     const int* __restrict__ taps,            // (TAPS, 2): dy, dx
-    int Mc, int YY_, int XX_, int y0, int x0, int S_,
-    int OH_, int OW_, int COUT, int XH_, int XW_, int CIN) {
-    const int S = GT ? (GT % 10) : S_;
-    const int OH = GT ? (GT / 1000) : OH_;
-    const int OW = GT ? (GT / 1000) : OW_;
-    const int XH = GT ? ((GT / 10) % 100) : XH_;
-    const int XW = GT ? ((GT / 10) % 100) : XW_;
-    // for both hot geometries XH/S equals the class grid extent for every
-    // parity offset (20/2=10, 9/1=9), keeping YY/XX compile-time under GT
-    const int YY = GT ? (XH / S) : YY_;
-    const int XX = GT ? (XW / S) : XX_;
-    const int COUTc = CO_T ? CO_T : COUT;
-    const int K = TAPS * COUTc;
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    int wr = (NCOL == 32) ? wave : (wave >> 1);
-    int wc = (NCOL == 32) ? 0 : (wave & 1);
-    long row0 = (long)blockIdx.x * (NCOL == 32 ? 128 : 64) + wr * 32;
-    long col0 = (long)blockIdx.y * 64 + wc * 32;
-    int frow = lane & 15;
-    int kseg = (lane >> 4) * 8;
+    int Mc, int y0, int x0) {
+    constexpr int S = G::S, OH = G::OH, OW = G::OW, COUT = G::COUT;
+    constexpr int XH = G::INH, XW = G::INW, CIN = G::CIN;
+    constexpr int K = G::TAPS * COUT;
+    constexpr unsigned XX = G::CLS_W, YX = G::CLS_H * G::CLS_W;
+    const WarpTile<tile_ncol<CIN>> wt;
+    const long row0 = wt.row0(), col0 = wt.col0();
 
-    const unsigned YX = (unsigned)(YY * XX);
+    // class row -> (n, y, x)
+    auto pixel = [&](unsigned r, unsigned& n, int& y, int& x) {
+        n = r / YX;
+        unsigned p = r % YX;
+        y = y0 + (int)(p / XX) * S;
+        x = x0 + (int)(p % XX) * S;
+    };
+
     long nbase[2];
     int yv[2], xv[2];
     bool avalid[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        unsigned r = (unsigned)row0 + i * 16 + frow;
+        unsigned r = (unsigned)row0 + i * 16 + wt.frow;
         avalid[i] = r < (unsigned)Mc;
-        unsigned n = avalid[i] ? r / YX : 0;
-        unsigned p = avalid[i] ? r % YX : 0;
-        yv[i] = y0 + (int)(p / (unsigned)XX) * S;
-        xv[i] = x0 + (int)(p % (unsigned)XX) * S;
+        unsigned n;
+        pixel(avalid[i] ? r : 0, n, yv[i], xv[i]);
         nbase[i] = (long)n * OH * OW;
     }
 
     f32x4 acc[2][2] = {};
     for (int k0 = 0; k0 < K; k0 += 32) {
-        int k = k0 + kseg;
-        int t = (unsigned)k / (unsigned)COUTc;
-        int co = (unsigned)k % (unsigned)COUTc;
+        int k = k0 + wt.kseg;
+        int t = (unsigned)k / (unsigned)COUT;
+        int co = (unsigned)k % (unsigned)COUT;
         int dy = taps[2 * t], dx = taps[2 * t + 1];
         bf16x8 a[2], b[2];
 #pragma unroll
@@ -362,10 +336,10 @@ __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
             int oy = ny / S, ox = nx / S;
             bool ok = avalid[i] && ny >= 0 && nx >= 0 && oy < OH && ox < OW;
             a[i] = ok
-                ? cload_bf16x8(dY + (nbase[i] + (long)oy * OW + ox) * COUT + co)
-                : czero();
-            long c = col0 + i * 16 + frow;
-            b[i] = (c < CIN) ? cload_bf16x8(Wd + c * K + k0 + kseg) : czero();
+                ? load_bf16x8(dY + (nbase[i] + (long)oy * OW + ox) * COUT + co)
+                : zero_bf16x8();
+            long c = col0 + i * 16 + wt.frow;
+            b[i] = (c < CIN) ? load_bf16x8(Wd + c * K + k) : zero_bf16x8();
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -375,28 +349,19 @@ __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
                     a[i], b[j], acc[i][j], 0, 0, 0);
     }
 
-    int ccol = lane & 15;
-    int crow = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long rr = row0 + i * 16 + crow + r;
-                long cc = col0 + j * 16 + ccol;
-                if (rr < Mc && cc < CIN) {
-                    unsigned n = (unsigned)rr / YX;
-                    unsigned p = (unsigned)rr % YX;
-                    int y = y0 + (int)(p / (unsigned)XX) * S;
-                    int x = x0 + (int)(p % (unsigned)XX) * S;
-                    long addr = (((long)n * XH + y) * XW + x) * CIN + cc;
-                    float v = acc[i][j][r];
-                    if (OUT_MASK)
-                        v = (bf2f(actx[addr]) > 0.f) ? v : 0.f;
-                    dX[addr] = f2bf(v);
-                }
-            }
+    for_each_acc(acc, wt.lane, [&](int r, int c, float v) {
+        long rr = row0 + r;
+        long cc = col0 + c;
+        if (rr < Mc && cc < CIN) {
+            unsigned n;
+            int y, x;
+            pixel((unsigned)rr, n, y, x);
+            long addr = (((long)n * XH + y) * XW + x) * CIN + cc;
+            if (OUT_MASK)
+                v = (bf2f(actx[addr]) > 0.f) ? v : 0.f;
+            dX[addr] = f2bf(v);
+        }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -404,106 +369,93 @@ __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
 // The FULL K extent (<= 576) and full COUT (<= 64) are staged per 32-row
 // tile, so dY and the patches are each read exactly once; per-wave
 // accumulators cover all k-tiles and are flushed with f32 atomics once per
-// chunk.  Fused ReLU mask + bias grad.
+// workgroup.  Fused ReLU mask + bias grad.
+//
+// WgradTile is everything the chunked and the band kernel share: the wave
+// split, the accumulators, one 32-row tile step (stage, gather, MFMA, bias
+// column sum) and the atomic flush.  The kernels differ only in where a patch
+// row comes from (global vs the LDS image) and in their outer loop.
 // ---------------------------------------------------------------------------
-// TORCH_LAYOUT: remap each (ky, kx, ci)-packed k store to torch's
-// (ci, ky, kx) weight order, so gradients accumulate straight into the
-// module's .grad view (compile-time dims -> cheap index math).
-template <bool IN_U8, int KH, int KW, int CIN, int S, int NCOT, bool RELU,
-          bool TORCH_LAYOUT = false>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(
-    const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
-    const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward output
-    const void* __restrict__ in,             // (N, INH, INW, CIN)
-    float* __restrict__ dWt,                 // (COUT, K) f32
-    float* __restrict__ db,                  // (COUT,) f32
-    int M, int INH, int INW, int OH, int OW, int COUT, int rows_per_chunk) {
-    constexpr int K = KH * KW * CIN;
-    constexpr int KWC = KW * CIN;
+template <class G>
+struct WgradTile {
+    static constexpr int K = G::K, COUT = G::COUT;
     // NCOT = co tiles of 32 (1 when COUT<=32): waves split K 4/NCOT ways so
     // no wave computes guarded-away co columns
-    constexpr int NKW = 4 / NCOT;                     // k splits
+    static constexpr int NCOT = (COUT + 31) / 32;
+    static constexpr int NKW = 4 / NCOT;              // k splits
     // per-wave k extent, in whole 16-col fragments (K = 64, the one-channel
     // conv1, gives each of the 4 waves exactly one fragment)
-    constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
-    constexpr int KFRAG = KHALF / 16;                 // 16-col frags per wave
-    __shared__ __hip_bfloat16 s_dy[32][64 + 8];
-    __shared__ __hip_bfloat16 s_a[32][K + 8];
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    int wr = (NCOT == 1) ? 0 : (wave >> 1);           // co tile
-    int wc = (NCOT == 1) ? wave : (wave & 1);         // k split
-    long mstart = (long)blockIdx.x * rows_per_chunk;
-    long mend = min((long)M, mstart + rows_per_chunk);
-    int frow = lane & 15;
-    int mseg = (lane >> 4) * 8;
+    static constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
+    static constexpr int KFRAG = KHALF / 16;          // 16-col frags per wave
+    static constexpr int LD_DY = 64 + 8, LD_A = K + 8;   // padded LDS rows
+    typedef __hip_bfloat16 DyTile[32][LD_DY];
+    typedef __hip_bfloat16 PatchTile[32][LD_A];
 
+    int lane;
+    int wr;     // co tile
+    int wc;     // k split
     // co extent per wave is always 32 (2 fragments of 16)
     f32x4 acc[2][KFRAG] = {};
     float bias_acc = 0.f;
 
-    for (long m0 = mstart; m0 < mend; m0 += 32) {
+    __device__ __forceinline__ WgradTile() {
+        int wave = threadIdx.x / WAVE;
+        lane = threadIdx.x & (WAVE - 1);
+        wr = (NCOT == 1) ? 0 : (wave >> 1);
+        wc = (NCOT == 1) ? wave : (wave & 1);
+    }
+
+    // One tile step over GEMM rows gm0 .. gm0+31, of which the first nvalid
+    // exist (the rest stage as zero).  patch_row(mrow, k) returns the 8 patch
+    // elements k..k+7 of row gm0 + mrow; it is only called for mrow < nvalid.
+    template <class PatchRow>
+    __device__ __forceinline__ void accumulate(
+        DyTile& s_dy, PatchTile& s_a,
+        const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
+        const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward output
+        long gm0, int nvalid, PatchRow&& patch_row) {
         __syncthreads();
-        {
-            int t = threadIdx.x;
-            {
-                int mrow = t / 8;
-                int col = (t % 8) * 8;
-                long gm = m0 + mrow;
-                bf16x8 v = czero();
-                if (gm < mend) {
+        int t = threadIdx.x;
+        {   // dY rows, masked by the forward output's ReLU
+            int mrow = t / 8;
+            int col = (t % 8) * 8;
+            long gm = gm0 + mrow;
+            bf16x8 v = zero_bf16x8();
+            if (mrow < nvalid) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        long c = col + e;
-                        float g = (c < COUT) ? bf2f(dY[gm * COUT + c]) : 0.f;
-                        if (RELU) {
-                            float m_ = (c < COUT) ? bf2f(act[gm * COUT + c]) : 0.f;
-                            g = (m_ > 0.f) ? g : 0.f;
-                        }
-                        v[e] = (__bf16)g;
-                    }
+                for (int e = 0; e < 8; ++e) {
+                    int c = col + e;
+                    float g = (c < COUT) ? bf2f(dY[gm * COUT + c]) : 0.f;
+                    float m_ = (c < COUT) ? bf2f(act[gm * COUT + c]) : 0.f;
+                    v[e] = (__bf16)((m_ > 0.f) ? g : 0.f);
                 }
-                *reinterpret_cast<bf16x8*>(&s_dy[mrow][col]) = v;
             }
-            for (int e8 = t; e8 < 32 * (K / 8); e8 += 256) {
-                int mrow = e8 / (K / 8);
-                int k = (e8 % (K / 8)) * 8;
-                long gm = m0 + mrow;
-                bf16x8 w = czero();
-                if (gm < mend) {
-                    unsigned n = (unsigned)gm / (unsigned)(OH * OW);
-                    unsigned p = (unsigned)gm % (unsigned)(OH * OW);
-                    int oy = p / (unsigned)OW, ox = p % (unsigned)OW;
-                    long base = (((long)n * INH + (long)oy * S) * INW
-                                 + (long)ox * S) * CIN;
-                    int dy_ = k / KWC, rem = k % KWC;
-                    long off = base + (long)dy_ * INW * CIN + rem;
-                    if (IN_U8)
-                        w = load_patch_u8<CIN>(
-                            reinterpret_cast<const unsigned char*>(in) + off);
-                    else
-                        w = cload_bf16x8(
-                            reinterpret_cast<const __hip_bfloat16*>(in) + off);
-                }
-                *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
-            }
+            *reinterpret_cast<bf16x8*>(&s_dy[mrow][col]) = v;
+        }
+        for (int e8 = t; e8 < 32 * (K / 8); e8 += 256) {
+            int mrow = e8 / (K / 8);
+            int k = (e8 % (K / 8)) * 8;
+            bf16x8 w = (mrow < nvalid) ? patch_row(mrow, k) : zero_bf16x8();
+            *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
         }
         __syncthreads();
 
         // fragment gathers via hardware transpose-reads (common.h)
+        int frow = lane & 15;
+        int mseg = (lane >> 4) * 8;
         bf16x8 fa[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            fa[i] = lds_col_frag8<64 + 8>(&s_dy[0][0], mseg,
-                                          wr * 32 + i * 16, lane);
+            fa[i] = lds_col_frag8<LD_DY>(&s_dy[0][0], mseg,
+                                         wr * 32 + i * 16, lane);
 #pragma unroll
         for (int kf = 0; kf < KFRAG; ++kf) {
             int kcol0 = wc * KHALF + kf * 16;
             bf16x8 fb;
             if (kcol0 + 16 <= K) {
-                fb = lds_col_frag8<K + 8>(&s_a[0][0], mseg, kcol0, lane);
+                fb = lds_col_frag8<LD_A>(&s_a[0][0], mseg, kcol0, lane);
             } else {                       // partial tail column span
-                fb = czero();
+                fb = zero_bf16x8();
                 int kcol = kcol0 + frow;
                 if (kcol < K) {
 #pragma unroll
@@ -523,30 +475,45 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
         }
     }
 
-    int ccol = lane & 15;
-    int crow = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int kf = 0; kf < KFRAG; ++kf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long co = wr * 32 + i * 16 + crow + r;
-                long kk = wc * KHALF + kf * 16 + ccol;
-                if (co < COUT && kk < K) {
-                    if (TORCH_LAYOUT) {
-                        int ci = (int)(kk % CIN);
-                        int t_ = (int)(kk / CIN);
-                        int kx = t_ % KW, ky = t_ / KW;
-                        kk = ((long)ci * KH + ky) * KW + kx;
-                    }
-                    atomicAdd(&dWt[co * K + kk], acc[i][kf][r]);
-                }
-            }
-    if (threadIdx.x < 64) {
-        long c = threadIdx.x;
-        if (c < COUT) atomicAdd(&db[c], bias_acc);
+    __device__ __forceinline__ void flush(float* __restrict__ dWt,  // (COUT, K)
+                                          float* __restrict__ db) { // (COUT,)
+        for_each_acc(acc, lane, [&](int r, int c, float v) {
+            long co = wr * 32 + r;
+            long kk = wc * KHALF + c;
+            if (co < COUT && kk < K) atomicAdd(&dWt[co * K + kk], v);
+        });
+        if (threadIdx.x < 64) {
+            long c = threadIdx.x;
+            if (c < COUT) atomicAdd(&db[c], bias_acc);
+        }
     }
+};
+
+// chunked wgrad: a workgroup owns rows_per_chunk GEMM rows; patch rows are
+// read from the global image.
+template <class G>
+__global__ __launch_bounds__(256) void conv_wgrad_kernel(
+    const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
+    const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward output
+    const void* __restrict__ in,             // (N, INH, INW, CIN)
+    float* __restrict__ dWt,                 // (COUT, K) f32
+    float* __restrict__ db,                  // (COUT,) f32
+    int M, int rows_per_chunk) {
+    __shared__ typename WgradTile<G>::DyTile s_dy;
+    __shared__ typename WgradTile<G>::PatchTile s_a;
+    WgradTile<G> tile;
+    long mstart = (long)blockIdx.x * rows_per_chunk;
+    long mend = min((long)M, mstart + rows_per_chunk);
+
+    for (long m0 = mstart; m0 < mend; m0 += 32)
+        tile.accumulate(s_dy, s_a, dY, act, m0, (int)min(32L, mend - m0),
+                        [&](int mrow, int k) {
+            long base = patch_origin<G>((unsigned)(m0 + mrow));
+            int dy_ = k / G::KWC, rem = k % G::KWC;
+            return load_patch_row<G>(
+                in, base + (long)dy_ * G::INW * G::CIN + rem);
+        });
+    tile.flush(dWt, db);
 }
 
 // ---------------------------------------------------------------------------
@@ -556,85 +523,64 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
 // instead of one per patch overlap: conv1 557 MB u8 re-dequant -> 154 MB,
 // conv3 9x re-read -> 1x).  Fused bias + ReLU as in conv_fwd_kernel.
 // ---------------------------------------------------------------------------
-// COUT_T: output columns computed per launch (always 32 — a 64-out conv
-// runs as two launches with co0 = 0/32, halving the LDS weight slab so
-// 2-3 workgroups fit per CU); COUT_FULL is the output row stride.
-template <bool IN_U8, int KH, int KW, int CIN, int S, int INH, int INW,
-          int OH, int OW, int COUT_T, int COUT_FULL>
+// BAND_COLS: output columns computed per launch — a 64-out conv runs as two
+// launches with co0 = 0/32, halving the LDS weight slab so 2-3 workgroups
+// fit per CU; G::COUT is the output row stride.
+constexpr int BAND_COLS = 32;
+
+template <class G>
 __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
     const void* __restrict__ in,            // (N, INH, INW, CIN)
-    const __hip_bfloat16* __restrict__ Wt,  // (COUT_FULL, K)
+    const __hip_bfloat16* __restrict__ Wt,  // (COUT, K)
     const float* __restrict__ bias,
-    __hip_bfloat16* __restrict__ out,       // (N*OH*OW, COUT_FULL)
+    __hip_bfloat16* __restrict__ out,       // (N*NPIX, COUT)
     int N, int imgs_per_wg, int co0) {
-    constexpr int K = KH * KW * CIN;
-    constexpr int KWC = KW * CIN;
-    constexpr int NPIX = OH * OW;
+    constexpr int K = G::K, NPIX = G::NPIX;
     constexpr int NB = 2;                          // B frags = 32 cols/wave
-    constexpr int RPI = 128;                       // 4 waves stack rows
 
-    __shared__ __hip_bfloat16 s_img[INH * INW * CIN];
-    __shared__ __hip_bfloat16 s_w[COUT_T][K + 8];
+    __shared__ __hip_bfloat16 s_img[G::IMG];
+    __shared__ __hip_bfloat16 s_w[BAND_COLS][K + 8];
 
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    int wr = wave;
-    int wc = 0;
-    int frow = lane & 15;
-    int kseg = (lane >> 4) * 8;
+    const WarpTile<BAND_COLS> wt;                  // 4 waves stack rows
 
-    for (int e = threadIdx.x * 8; e < COUT_T * K; e += blockDim.x * 8) {
+    for (int e = threadIdx.x * 8; e < BAND_COLS * K; e += blockDim.x * 8) {
         int c = e / K, k = e % K;
         *reinterpret_cast<bf16x8*>(&s_w[c][k]) =
-            cload_bf16x8(Wt + (long)(co0 + c) * K + k);
+            load_bf16x8(Wt + (long)(co0 + c) * K + k);
     }
 
     const long n0 = (long)blockIdx.x * imgs_per_wg;
     const long n1 = min((long)N, n0 + imgs_per_wg);
     for (long n = n0; n < n1; ++n) {
         __syncthreads();
-        {
-            const long gbase = n * INH * INW * CIN;
-            for (int e = threadIdx.x * 8; e < INH * INW * CIN;
-                 e += blockDim.x * 8) {
-                bf16x8 v;
-                if (IN_U8)
-                    v = load_dequant8(
-                        reinterpret_cast<const unsigned char*>(in) + gbase + e);
-                else
-                    v = cload_bf16x8(
-                        reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
-                *reinterpret_cast<bf16x8*>(&s_img[e]) = v;
-            }
-        }
+        stage_image<G>(s_img, in, n);
         __syncthreads();
 
-        for (int p0 = wr * 32; p0 < NPIX; p0 += RPI) {
+        for (int p0 = wt.wr * 32; p0 < NPIX; p0 += wt.ROWS) {
             int pbase[2];
             bool pval[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                int pp = p0 + i * 16 + frow;
+                int pp = p0 + i * 16 + wt.frow;
                 pval[i] = pp < NPIX;
-                int oy = pp / OW, ox = pp % OW;
-                pbase[i] = ((oy * S) * INW + ox * S) * CIN;
+                int oy = pp / G::OW, ox = pp % G::OW;
+                pbase[i] = ((oy * G::S) * G::INW + ox * G::S) * G::CIN;
             }
             f32x4 acc[2][NB] = {};
             for (int k0 = 0; k0 < K; k0 += 32) {
-                int k = k0 + kseg;
-                int dy = k / KWC;
-                int rem = k % KWC;
-                int off = dy * INW * CIN + rem;
+                int k = k0 + wt.kseg;
+                int dy = k / G::KWC;
+                int rem = k % G::KWC;
+                int off = dy * G::INW * G::CIN + rem;
                 bf16x8 a[2], b[NB];
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
                     a[i] = pval[i]
-                        ? lds_patch_row<CIN>(&s_img[pbase[i] + off])
-                        : czero();
+                        ? lds_patch_row<G::CIN>(&s_img[pbase[i] + off])
+                        : zero_bf16x8();
 #pragma unroll
                 for (int j = 0; j < NB; ++j)
-                    b[j] = cload_bf16x8(
-                        &s_w[wc * 32 + j * 16 + frow][k0 + kseg]);
+                    b[j] = load_bf16x8(&s_w[wt.wc * 32 + j * 16 + wt.frow][k]);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -642,22 +588,15 @@ __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                             a[i], b[j], acc[i][j], 0, 0, 0);
             }
-            int ccol = lane & 15;
-            int crow = (lane >> 4) * 4;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int pp = p0 + i * 16 + crow + r;
-                        int cc = wc * 32 + j * 16 + ccol;
-                        if (pp < NPIX) {
-                            float v = acc[i][j][r] + bias[co0 + cc];
-                            out[(n * NPIX + pp) * COUT_FULL + co0 + cc] =
-                                f2bf(fmaxf(v, 0.f));
-                        }
-                    }
+            for_each_acc(acc, wt.lane, [&](int r, int c, float v) {
+                int pp = p0 + r;
+                int cc = wt.wc * 32 + c;
+                if (pp < NPIX) {
+                    v += bias[co0 + cc];
+                    out[(n * NPIX + pp) * G::COUT + co0 + cc] =
+                        f2bf(fmaxf(v, 0.f));
+                }
+            });
         }
     }
 }
@@ -667,165 +606,72 @@ __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
 // every Nature-CNN conv (conv1 84x84x4 u8->bf16 56 KB, conv2 20x20x32
 // 26 KB, conv3 9x9x64 10 KB), so one workgroup stages it ONCE (single
 // dequant per input element instead of one per patch overlap), rebuilds
-// each 32-row patch tile LDS->LDS, and accumulates the whole image's
-// contribution in registers with ONE atomic flush at the end.  Fragments
-// gathered by hardware transpose-reads.  Replaces conv_wgrad_kernel's
-// global patch re-reads (conv1: 557 MB -> 154 MB per step).
+// each 32-row patch tile LDS->LDS, and accumulates its images' whole
+// contribution in registers with ONE atomic flush at the end.  Replaces
+// conv_wgrad_kernel's global patch re-reads (conv1: 557 MB -> 154 MB per
+// step).
 // ---------------------------------------------------------------------------
-template <bool IN_U8, int KH, int KW, int CIN, int S, int INH, int INW,
-          int OH, int OW, int COUT_T>
+template <class G>
 __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
-    const __hip_bfloat16* __restrict__ dY,   // (M=N*OH*OW, COUT) PRE-MASKED
+    const __hip_bfloat16* __restrict__ dY,   // (M=N*NPIX, COUT)
     const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward out (mask)
     const void* __restrict__ in,             // (N, INH, INW, CIN)
     float* __restrict__ dWt,                 // (COUT, K) f32
     float* __restrict__ db,                  // (COUT,) f32
     int N, int imgs_per_wg) {
-    constexpr int K = KH * KW * CIN;
-    constexpr int KWC = KW * CIN;
-    constexpr int NPIX = OH * OW;
-    constexpr int NCOT = (COUT_T + 31) / 32;          // cout tiles of 32
-    constexpr int NKW = 4 / NCOT;                     // k splits
-    constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
-    constexpr int KFRAG = KHALF / 16;
-
-    __shared__ __hip_bfloat16 s_img[INH * INW * CIN];
-    __shared__ __hip_bfloat16 s_dy[32][64 + 8];
-    __shared__ __hip_bfloat16 s_a[32][K + 8];
-
-    int wave = threadIdx.x / WAVE;
-    int lane = threadIdx.x & (WAVE - 1);
-    int wr = (NCOT == 1) ? 0 : (wave >> 1);
-    int wc = (NCOT == 1) ? wave : (wave & 1);
-    int frow = lane & 15;
-    int mseg = (lane >> 4) * 8;
-
-    f32x4 acc[2][KFRAG] = {};
-    float bias_acc = 0.f;
+    constexpr int NPIX = G::NPIX;
+    __shared__ __hip_bfloat16 s_img[G::IMG];
+    __shared__ typename WgradTile<G>::DyTile s_dy;
+    __shared__ typename WgradTile<G>::PatchTile s_a;
+    WgradTile<G> tile;
 
     const long n0 = (long)blockIdx.x * imgs_per_wg;
     const long n1 = min((long)N, n0 + imgs_per_wg);
     for (long n = n0; n < n1; ++n) {
+        // s_img is read only while a patch tile is staged, i.e. before
+        // accumulate()'s second barrier; this one keeps the restage behind
+        // the previous image's last tile as a whole
         __syncthreads();
-        {   // stage the whole input image (dequant once per element)
-            const long gbase = n * INH * INW * CIN;
-            for (int e = threadIdx.x * 8; e < INH * INW * CIN;
-                 e += blockDim.x * 8) {
-                bf16x8 v;
-                if (IN_U8)
-                    v = load_dequant8(
-                        reinterpret_cast<const unsigned char*>(in) + gbase + e);
-                else
-                    v = cload_bf16x8(
-                        reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
-                *reinterpret_cast<bf16x8*>(&s_img[e]) = v;
-            }
-        }
-        for (int p0 = 0; p0 < NPIX; p0 += 32) {
-            __syncthreads();
-            {   // dY rows (pre-masked by the producing kernel; `act` kept
-                // for the generic path) + patch rows from the LDS image
-                int t = threadIdx.x;
-                {
-                    int mrow = t / 8;
-                    int col = (t % 8) * 8;
-                    int pp = p0 + mrow;
-                    bf16x8 v = czero();
-                    if (pp < NPIX) {
-                        long gm = n * NPIX + pp;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            float g = (col + e < COUT_T)
-                                ? bf2f(dY[gm * COUT_T + col + e]) : 0.f;
-                            float m_ = (col + e < COUT_T)
-                                ? bf2f(act[gm * COUT_T + col + e]) : 0.f;
-                            v[e] = (__bf16)((m_ > 0.f) ? g : 0.f);
-                        }
-                    }
-                    *reinterpret_cast<bf16x8*>(&s_dy[mrow][col]) = v;
-                }
-                for (int e8 = t; e8 < 32 * (K / 8); e8 += 256) {
-                    int mrow = e8 / (K / 8);
-                    int k = (e8 % (K / 8)) * 8;
-                    int pp = p0 + mrow;
-                    bf16x8 w = czero();
-                    if (pp < NPIX) {
-                        int oy = pp / OW, ox = pp % OW;
-                        int dy_ = k / KWC, rem = k % KWC;
-                        w = lds_patch_row<CIN>(
-                            &s_img[((oy * S + dy_) * INW + ox * S) * CIN + rem]);
-                    }
-                    *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
-                }
-            }
-            __syncthreads();
-
-            bf16x8 fa[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                fa[i] = lds_col_frag8<64 + 8>(&s_dy[0][0], mseg,
-                                              wr * 32 + i * 16, lane);
-#pragma unroll
-            for (int kf = 0; kf < KFRAG; ++kf) {
-                int kcol0 = wc * KHALF + kf * 16;
-                bf16x8 fb;
-                if (kcol0 + 16 <= K) {
-                    fb = lds_col_frag8<K + 8>(&s_a[0][0], mseg, kcol0, lane);
-                } else {
-                    fb = czero();
-                    int kcol = kcol0 + frow;
-                    if (kcol < K) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            fb[e] = *(const __bf16*)&s_a[mseg + e][kcol];
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-                    acc[i][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        fa[i], fb, acc[i][kf], 0, 0, 0);
-            }
-            if (threadIdx.x < 64) {
-                int c = threadIdx.x;
-                for (int mr = 0; mr < 32; ++mr)
-                    bias_acc += bf2f(s_dy[mr][c]);
-            }
-        }
+        stage_image<G>(s_img, in, n);
+        for (int p0 = 0; p0 < NPIX; p0 += 32)
+            tile.accumulate(s_dy, s_a, dY, act, n * NPIX + p0, NPIX - p0,
+                            [&](int mrow, int k) {
+                int pp = p0 + mrow;
+                int oy = pp / G::OW, ox = pp % G::OW;
+                int dy_ = k / G::KWC, rem = k % G::KWC;
+                return lds_patch_row<G::CIN>(
+                    &s_img[((oy * G::S + dy_) * G::INW + ox * G::S) * G::CIN
+                           + rem]);
+            });
     }
-
-    int ccol = lane & 15;
-    int crow = (lane >> 4) * 4;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int kf = 0; kf < KFRAG; ++kf)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long co = wr * 32 + i * 16 + crow + r;
-                long kk = wc * KHALF + kf * 16 + ccol;
-                if (co < COUT_T && kk < K)
-                    atomicAdd(&dWt[co * K + kk], acc[i][kf][r]);
-            }
-    if (threadIdx.x < 64) {
-        long c = threadIdx.x;
-        if (c < COUT_T) atomicAdd(&db[c], bias_acc);
-    }
+    tile.flush(dWt, db);
 }
 
 // ---------------------------------------------------------------------------
-// Host wrappers.  Conv geometry is dispatched over the three Nature-CNN
-// layers (and reusable for any conv matching a template instance).
+// Host wrappers
 // ---------------------------------------------------------------------------
 
-static inline int ccdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// conv_id: 1 = Conv1<cin1> (cin1 taken from the input's channel dimension),
+//          2 = Conv2, 3 = Conv3.  Calls f with a value of the layer's type.
+template <class F>
+static void dispatch_layer(int64_t conv_id, int cin1, const char* who, F&& f) {
+    if (conv_id == 1 && cin1 == 1) f(Conv1<1>{});
+    else if (conv_id == 1 && cin1 == 4) f(Conv1<4>{});
+    else if (conv_id == 2) f(Conv2{});
+    else if (conv_id == 3) f(Conv3{});
+    else TORCH_CHECK(false, who, ": unknown conv_id ", conv_id);
+}
 
 // conv1 input guard.  The kernels index the frames as a dense (N, INH, INW,
 // CIN) u8 array and load them `wide` bytes at a time from data_ptr, so a
 // strided view or a base pointer off that alignment must raise here, before
-// any launch.  Returns CIN (1 = single frame, 4 = frame stack); `wide1` /
-// `wide4` are the widest global load the chosen kernel issues per variant.
-static int conv1_cin(const torch::Tensor& in, int64_t N, int64_t INH,
-                     int64_t INW, int wide1, int wide4, const char* who) {
+// any launch.  Returns CIN (1 = single frame, 4 = frame stack), 0 for the
+// other layers; `wide1` / `wide4` are the widest global load the chosen
+// kernel issues per variant.
+static int conv1_cin(int64_t conv_id, const torch::Tensor& in, int64_t N,
+                     int wide1, int wide4, const char* who) {
+    if (conv_id != 1) return 0;
+    constexpr int64_t INH = Conv1<4>::INH, INW = Conv1<4>::INW;
     TORCH_CHECK(in.is_cuda() && in.dtype() == torch::kUInt8, who,
                 ": conv1 input must be a uint8 device tensor");
     TORCH_CHECK(in.dim() == 4 && in.size(0) == N && in.size(1) == INH
@@ -842,212 +688,189 @@ static int conv1_cin(const torch::Tensor& in, int64_t N, int64_t INH,
     return (int)C;
 }
 
-static void conv1_wt_check(const torch::Tensor& Wt, int cin, const char* who) {
-    TORCH_CHECK(Wt.dim() == 2 && Wt.size(0) == 32 && Wt.size(1) == 64 * cin,
-                who, ": conv1 weights must be (32, ", 64 * cin, "), got ",
+// the bf16 layers take the previous layer's (N*NPIX, COUT) output as their
+// (N, INH, INW, CIN) input: same elements, so only the count is checked
+template <class G>
+static void check_input(const torch::Tensor& in, int64_t N, const char* who) {
+    if (G::IN_U8) return;                      // conv1_cin has checked it
+    TORCH_CHECK(in.is_cuda() && in.dtype() == torch::kBFloat16
+                && in.is_contiguous() && in.numel() == N * G::IMG, who,
+                ": input must be a contiguous bf16 device tensor of ", N, " x ",
+                G::INH, " x ", G::INW, " x ", G::CIN, " elements");
+}
+
+template <class G>
+static void check_weights(const torch::Tensor& Wt, const char* who) {
+    TORCH_CHECK(Wt.dim() == 2 && Wt.size(0) == G::COUT && Wt.size(1) == G::K,
+                who, ": weights must be (", G::COUT, ", ", G::K, "), got ",
                 Wt.sizes());
 }
 
-// conv_id: 1 = 8x8 s4 u8-in, CIN 1 or 4 (taken from in.size(3)),
-//          2 = 4x4 s2 CIN 32, 3 = 3x3 s1 CIN 64
+template <class G>
+static void check_grads(const torch::Tensor& dY, const torch::Tensor& act,
+                        int64_t N, const char* who) {
+    TORCH_CHECK(dY.numel() == N * G::NPIX * G::COUT
+                && act.numel() == dY.numel(), who, ": dY/act must be (N*",
+                G::NPIX, ", ", G::COUT, ")");
+}
+
+// the geometry arguments of the classic entry points must name the layer
+template <class G>
+static void check_geometry(int64_t INH, int64_t INW, int64_t OH, int64_t OW,
+                           int64_t COUT, int64_t K, const char* who) {
+    TORCH_CHECK(INH == G::INH && INW == G::INW && OH == G::OH && OW == G::OW
+                && COUT == G::COUT && K == G::K, who,
+                ": this layer is ", G::INH, "x", G::INW, " -> ", G::OH, "x",
+                G::OW, ", COUT ", G::COUT, ", K ", G::K, "; got ", INH, "x",
+                INW, " -> ", OH, "x", OW, ", COUT ", COUT, ", K ", K);
+}
+
 torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
                        int64_t conv_id, int64_t N, int64_t INH, int64_t INW,
                        int64_t OH, int64_t OW, bool relu) {
-    long M = N * OH * OW;
-    long COUT = Wt.size(0);
-    auto out = torch::empty({M, COUT},
-                            in.options().dtype(torch::kBFloat16));
-    dim3 grid(ccdiv(M, COUT <= 32 ? 128 : 64), ccdiv(COUT, 64));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    auto* w = reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr());
-    auto* o = reinterpret_cast<__hip_bfloat16*>(out.data_ptr());
-    const float* b = bias.data_ptr<float>();
-    const void* x = in.data_ptr();
-#define CLAUNCH(U8, KH_, KW_, CIN_, S_)                                        \
-    hipLaunchKernelGGL((conv_fwd_kernel<U8, KH_, KW_, CIN_, S_, 64, true>),    \
-                       grid,                                                   \
-                       dim3(256), 0, stream.stream(), x, w, b, o, (int)M,      \
-                       (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT)
-#define C1LAUNCH(CIN_)                                                         \
-    hipLaunchKernelGGL((conv_fwd_kernel<true, 8, 8, CIN_, 4, 32, true>), grid, \
-                       dim3(256), 0, stream.stream(), x, w, b, o, (int)M,      \
-                       (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT)
-    if (conv_id == 1) {
-        TORCH_CHECK((OH - 1) * 4 + 8 <= INH && (OW - 1) * 4 + 8 <= INW,
-                    "conv_fwd: conv1 output extent exceeds the input");
-        int cin = conv1_cin(in, N, INH, INW, 4, 8, "conv_fwd");
-        conv1_wt_check(Wt, cin, "conv_fwd");
-        if (cin == 1) C1LAUNCH(1);
-        else C1LAUNCH(4);
-    } else if (conv_id == 2) {
-        TORCH_CHECK(in.dtype() == torch::kBFloat16);
-        CLAUNCH(false, 4, 4, 32, 2);
-    } else if (conv_id == 3) {
-        CLAUNCH(false, 3, 3, 64, 1);
-    } else {
-        TORCH_CHECK(false, "unknown conv_id");
-    }
-#undef C1LAUNCH
-#undef CLAUNCH
+    const char* who = "conv_fwd";
+    torch::Tensor out;
+    int cin1 = conv1_cin(conv_id, in, N, 4, 8, who);
+    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        check_weights<G>(Wt, who);
+        check_geometry<G>(INH, INW, OH, OW, Wt.size(0), Wt.size(1), who);
+        check_input<G>(in, N, who);
+        long M = N * G::NPIX;
+        out = torch::empty({M, G::COUT}, in.options().dtype(torch::kBFloat16));
+        dim3 grid(cdiv(M, WarpTile<tile_ncol<G::COUT>>::ROWS),
+                  cdiv(G::COUT, 64));
+        hipLaunchKernelGGL(
+            (conv_fwd_kernel<G, true>), grid, dim3(256), 0,
+            at::cuda::getCurrentCUDAStream().stream(), in.data_ptr(),
+            reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr()),
+            bias.data_ptr<float>(),
+            reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), (int)M);
+    });
     return out;
-}
-
-torch::Tensor conv_dgrad(torch::Tensor dYp, torch::Tensor Wd, torch::Tensor taps,
-                         int64_t N, int64_t PH, int64_t PW, int64_t COUT,
-                         int64_t XH, int64_t XW, int64_t CIN,
-                         int64_t y0, int64_t x0, int64_t S, int64_t pad,
-                         torch::Tensor dX) {
-    long YY = (XH - 1 - y0) / S + 1;
-    long XX = (XW - 1 - x0) / S + 1;
-    long Mc = N * YY * XX;
-    long TAPS = taps.size(0);
-    dim3 grid(ccdiv(Mc, CIN <= 32 ? 128 : 64), ccdiv(CIN, 64));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    auto* dy = reinterpret_cast<const __hip_bfloat16*>(dYp.data_ptr());
-    auto* w = reinterpret_cast<const __hip_bfloat16*>(Wd.data_ptr());
-    auto* dx = reinterpret_cast<__hip_bfloat16*>(dX.data_ptr());
-    const int* tp = taps.data_ptr<int>();
-#define DL1(T, NC, CO)                                                         \
-    hipLaunchKernelGGL((conv_dgrad_kernel<T, NC, CO>), grid, dim3(256), 0,     \
-                       stream.stream(), dy, w, dx, tp, (int)Mc, (int)YY,       \
-                       (int)XX, (int)y0, (int)x0, (int)S, (int)pad, (int)PH,   \
-                       (int)PW, (int)COUT, (int)XH, (int)XW, (int)CIN)
-#define DLAUNCH(T)                                                             \
-    if (CIN <= 32) { if (COUT == 64) DL1(T, 32, 64); else DL1(T, 32, 0); }     \
-    else { if (COUT == 64) DL1(T, 64, 64); else DL1(T, 64, 0); }
-    if (TAPS == 4) { DLAUNCH(4); }
-    else if (TAPS == 9) { DLAUNCH(9); }
-    else TORCH_CHECK(false, "unsupported tap count");
-#undef DLAUNCH
-#undef DL1
-    return dX;
 }
 
 // dense-input dgrad: dY is the UNPADDED, PRE-MASKED upstream gradient
 // (N, OH, OW, COUT); actx (optional) fuses the ReLU mask of the conv below
-// into the dX store.
+// into the dX store.  Instantiated for conv3 and conv2 (conv1 has no dX).
+template <class G>
+static bool dgrad_dense_is(int64_t OH, int64_t OW, int64_t COUT, int64_t XH,
+                           int64_t XW, int64_t CIN, int64_t S) {
+    return OH == G::OH && OW == G::OW && COUT == G::COUT && XH == G::INH
+           && XW == G::INW && CIN == G::CIN && S == G::S;
+}
+
+template <class G>
+static void dgrad_dense_launch(const torch::Tensor& dY, const torch::Tensor& Wd,
+                               const torch::Tensor& taps,
+                               const torch::Tensor& actx, int64_t N,
+                               int64_t y0, int64_t x0, torch::Tensor& dX) {
+    const char* who = "conv_dgrad_dense";
+    TORCH_CHECK(taps.dtype() == torch::kInt32 && taps.dim() == 2
+                && taps.size(0) == G::TAPS && taps.size(1) == 2, who,
+                ": taps must be int32 (", G::TAPS, ", 2), got ", taps.sizes());
+    TORCH_CHECK(Wd.dim() == 2 && Wd.size(0) == G::CIN
+                && Wd.size(1) == G::TAPS * G::COUT, who, ": Wd must be (",
+                G::CIN, ", ", G::TAPS * G::COUT, "), got ", Wd.sizes());
+    TORCH_CHECK(dY.numel() == N * G::NPIX * G::COUT && dX.numel() == N * G::IMG,
+                who, ": dY must hold N*", G::NPIX * G::COUT, " and dX N*",
+                G::IMG, " elements for N = ", N);
+    TORCH_CHECK(y0 >= 0 && y0 < G::S && x0 >= 0 && x0 < G::S, who,
+                ": parity offsets must lie in [0, ", G::S, ")");
+    bool has_m = actx.defined() && actx.numel() > 0;
+    if (has_m) TORCH_CHECK(actx.numel() == dX.numel());
+    long Mc = N * G::CLS_H * G::CLS_W;
+    dim3 grid(cdiv(Mc, WarpTile<tile_ncol<G::CIN>>::ROWS), cdiv(G::CIN, 64));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(
+            kernel, grid, dim3(256), 0,
+            at::cuda::getCurrentCUDAStream().stream(),
+            reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+            reinterpret_cast<const __hip_bfloat16*>(Wd.data_ptr()),
+            has_m ? reinterpret_cast<const __hip_bfloat16*>(actx.data_ptr())
+                  : nullptr,
+            reinterpret_cast<__hip_bfloat16*>(dX.data_ptr()),
+            taps.data_ptr<int>(), (int)Mc, (int)y0, (int)x0);
+    };
+    if (has_m) launch(conv_dgrad_dense_kernel<G, true>);
+    else launch(conv_dgrad_dense_kernel<G, false>);
+}
+
 torch::Tensor conv_dgrad_dense(torch::Tensor dY, torch::Tensor Wd,
                                torch::Tensor taps, torch::Tensor actx,
                                int64_t N, int64_t OH, int64_t OW, int64_t COUT,
                                int64_t XH, int64_t XW, int64_t CIN,
                                int64_t y0, int64_t x0, int64_t S,
                                torch::Tensor dX) {
-    long YY = (XH - 1 - y0) / S + 1;
-    long XX = (XW - 1 - x0) / S + 1;
-    long Mc = N * YY * XX;
-    long TAPS = taps.size(0);
-    bool has_m = actx.defined() && actx.numel() > 0;
-    if (has_m) TORCH_CHECK(actx.numel() == dX.numel());
-    dim3 grid(ccdiv(Mc, CIN <= 32 ? 128 : 64), ccdiv(CIN, 64));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    auto* dy = reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr());
-    auto* w = reinterpret_cast<const __hip_bfloat16*>(Wd.data_ptr());
-    auto* am = has_m
-        ? reinterpret_cast<const __hip_bfloat16*>(actx.data_ptr()) : nullptr;
-    auto* dx = reinterpret_cast<__hip_bfloat16*>(dX.data_ptr());
-    const int* tp = taps.data_ptr<int>();
-#define DD1(T, NC, CO, OM, GT)                                                 \
-    hipLaunchKernelGGL((conv_dgrad_dense_kernel<T, NC, CO, OM, GT>), grid,     \
-                       dim3(256), 0, stream.stream(), dy, w, am, dx, tp,       \
-                       (int)Mc, (int)YY, (int)XX, (int)y0, (int)x0, (int)S,    \
-                       (int)OH, (int)OW, (int)COUT, (int)XH, (int)XW, (int)CIN)
-#define DDM(T, NC, CO, GT)                                                     \
-    do { if (has_m) DD1(T, NC, CO, true, GT);                                  \
-         else DD1(T, NC, CO, false, GT); } while (0)
-    // compile-time geometry for the hot Nature shapes (address math
-    // lowers to mul-shift; GT = OH*1000 + XH*10 + S)
-    if (TAPS == 9 && CIN == 64 && COUT == 64 && OH == 7 && XH == 9 && S == 1) {
-        DDM(9, 64, 64, 7091);
-        return dX;
-    }
-    if (TAPS == 4 && CIN == 32 && COUT == 64 && OH == 9 && XH == 20 && S == 2) {
-        DDM(4, 32, 64, 9202);
-        return dX;
-    }
-#define DDLAUNCH(T)                                                            \
-    if (CIN <= 32) { if (COUT == 64) DDM(T, 32, 64, 0); else DDM(T, 32, 0, 0); } \
-    else { if (COUT == 64) DDM(T, 64, 64, 0); else DDM(T, 64, 0, 0); }
-    if (TAPS == 4) { DDLAUNCH(4); }
-    else if (TAPS == 9) { DDLAUNCH(9); }
-    else TORCH_CHECK(false, "unsupported tap count");
-#undef DDLAUNCH
-#undef DDM
-#undef DD1
+    if (dgrad_dense_is<Conv3>(OH, OW, COUT, XH, XW, CIN, S))
+        dgrad_dense_launch<Conv3>(dY, Wd, taps, actx, N, y0, x0, dX);
+    else if (dgrad_dense_is<Conv2>(OH, OW, COUT, XH, XW, CIN, S))
+        dgrad_dense_launch<Conv2>(dY, Wd, taps, actx, N, y0, x0, dX);
+    else
+        TORCH_CHECK(false, "conv_dgrad_dense: only conv3 (", Conv3::OH, "x",
+                    Conv3::OW, "x", Conv3::COUT, " -> ", Conv3::INH, "x",
+                    Conv3::INW, "x", Conv3::CIN, ", stride ", Conv3::S,
+                    ") and conv2 (", Conv2::OH, "x", Conv2::OW, "x",
+                    Conv2::COUT, " -> ", Conv2::INH, "x", Conv2::INW, "x",
+                    Conv2::CIN, ", stride ", Conv2::S,
+                    ") are instantiated; got ", OH, "x", OW, "x", COUT, " -> ",
+                    XH, "x", XW, "x", CIN, ", stride ", S);
     return dX;
 }
 
-// per-image band forward for the three Nature-CNN geometries.
+// per-image band forward.  N = number of images (B*T).
 torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
                             torch::Tensor bias, int64_t conv_id, int64_t N) {
-    long COUT = (conv_id == 1) ? 32 : 64;
-    long NPIX = (conv_id == 1) ? 400 : (conv_id == 2) ? 81 : 49;
-    auto out = torch::empty({N * NPIX, COUT},
-                            in.options().dtype(torch::kBFloat16));
-    int imgs = (int)((N + 2047) / 2048);
-    int grid = (int)((N + imgs - 1) / imgs);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    const void* x = in.data_ptr();
-    auto* w = reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr());
-    const float* b = bias.data_ptr<float>();
-    auto* o = reinterpret_cast<__hip_bfloat16*>(out.data_ptr());
-#define FBLAUNCH(U8, KH_, KW_, CIN_, S_, INH_, OH_, COF_, CO0_)                \
-    hipLaunchKernelGGL((conv_fwd_band_kernel<U8, KH_, KW_, CIN_, S_, INH_,     \
-                                             INH_, OH_, OH_, 32, COF_>),       \
-                       dim3(grid), dim3(256), 0, stream.stream(), x, w, b, o,  \
-                       (int)N, imgs, CO0_)
-    if (conv_id == 1) {
-        // whole-image staging loads 8 bytes per lane for both variants
-        int cin = conv1_cin(in, N, 84, 84, 8, 8, "conv_fwd_band");
-        conv1_wt_check(Wt, cin, "conv_fwd_band");
-        if (cin == 1) FBLAUNCH(true, 8, 8, 1, 4, 84, 20, 32, 0);
-        else FBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32, 0);
-    } else if (conv_id == 2) {   // 64-out: two 32-col launches (LDS halved)
-        FBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64, 0);
-        FBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64, 32);
-    } else if (conv_id == 3) {
-        FBLAUNCH(false, 3, 3, 64, 1, 9, 7, 64, 0);
-        FBLAUNCH(false, 3, 3, 64, 1, 9, 7, 64, 32);
-    } else {
-        TORCH_CHECK(false, "unknown conv_id");
-    }
-#undef FBLAUNCH
+    const char* who = "conv_fwd_band";
+    torch::Tensor out;
+    // whole-image staging loads 8 bytes per lane for both conv1 variants
+    int cin1 = conv1_cin(conv_id, in, N, 8, 8, who);
+    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        check_weights<G>(Wt, who);
+        check_input<G>(in, N, who);
+        out = torch::empty({N * G::NPIX, G::COUT},
+                           in.options().dtype(torch::kBFloat16));
+        int imgs = cdiv(N, 2048);
+        int grid = cdiv(N, imgs);
+        // a 64-out layer runs as two 32-col launches (LDS weight slab halved)
+        for (int co0 = 0; co0 < G::COUT; co0 += BAND_COLS)
+            hipLaunchKernelGGL(
+                (conv_fwd_band_kernel<G>), dim3(grid), dim3(256), 0,
+                at::cuda::getCurrentCUDAStream().stream(), in.data_ptr(),
+                reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr()),
+                bias.data_ptr<float>(),
+                reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), (int)N,
+                imgs, co0);
+    });
     return out;
 }
 
-// per-image band wgrad for the three Nature-CNN geometries (compile-time
-// shapes; see conv_wgrad_band_kernel).  N = number of images (B*T).
+// per-image band wgrad (see conv_wgrad_band_kernel).  N = number of images.
 std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
                                            torch::Tensor in, int64_t conv_id,
                                            int64_t N) {
-    long COUT = (conv_id == 1) ? 32 : 64;
+    const char* who = "conv_wgrad_band";
+    torch::Tensor dWt, db;
     // whole-image staging loads 8 bytes per lane for both conv1 variants
-    int cin1 = (conv_id == 1)
-        ? conv1_cin(in, N, 84, 84, 8, 8, "conv_wgrad_band") : 0;
-    long K = (conv_id == 1) ? 8 * 8 * cin1 : (conv_id == 2) ? 4 * 4 * 32
-                                                            : 3 * 3 * 64;
-    if (conv_id == 1)
-        TORCH_CHECK(dY.numel() == N * 400 * 32 && act.numel() == dY.numel(),
-                    "conv_wgrad_band: conv1 dY/act must be (N*400, 32)");
-    auto dWt = torch::zeros({COUT, K}, dY.options().dtype(torch::kFloat32));
-    auto db = torch::zeros({COUT}, dY.options().dtype(torch::kFloat32));
-    int imgs = (int)((N + 1023) / 1024);
-    int grid = (int)((N + imgs - 1) / imgs);
-    auto stream = at::cuda::getCurrentCUDAStream();
-    auto* dy = reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr());
-    auto* ac = reinterpret_cast<const __hip_bfloat16*>(act.data_ptr());
-    const void* x = in.data_ptr();
-#define WBLAUNCH(U8, KH_, KW_, CIN_, S_, INH_, OH_, CO_)                       \
-    hipLaunchKernelGGL((conv_wgrad_band_kernel<U8, KH_, KW_, CIN_, S_, INH_,   \
-                                               INH_, OH_, OH_, CO_>),          \
-                       dim3(grid), dim3(256), 0, stream.stream(), dy, ac, x,   \
-                       dWt.data_ptr<float>(), db.data_ptr<float>(), (int)N,    \
-                       imgs)
-    if (conv_id == 1 && cin1 == 1) WBLAUNCH(true, 8, 8, 1, 4, 84, 20, 32);
-    else if (conv_id == 1) WBLAUNCH(true, 8, 8, 4, 4, 84, 20, 32);
-    else if (conv_id == 2) WBLAUNCH(false, 4, 4, 32, 2, 20, 9, 64);
-    else if (conv_id == 3) WBLAUNCH(false, 3, 3, 64, 1, 9, 7, 64);
-    else TORCH_CHECK(false, "unknown conv_id");
-#undef WBLAUNCH
+    int cin1 = conv1_cin(conv_id, in, N, 8, 8, who);
+    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        check_input<G>(in, N, who);
+        check_grads<G>(dY, act, N, who);
+        dWt =
+            torch::zeros({G::COUT, G::K}, dY.options().dtype(torch::kFloat32));
+        db = torch::zeros({G::COUT}, dY.options().dtype(torch::kFloat32));
+        int imgs = cdiv(N, 1024);
+        int grid = cdiv(N, imgs);
+        hipLaunchKernelGGL(
+            (conv_wgrad_band_kernel<G>), dim3(grid), dim3(256), 0,
+            at::cuda::getCurrentCUDAStream().stream(),
+            reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+            reinterpret_cast<const __hip_bfloat16*>(act.data_ptr()),
+            in.data_ptr(), dWt.data_ptr<float>(), db.data_ptr<float>(), (int)N,
+            imgs);
+    });
     return {dWt, db};
 }
 
@@ -1056,40 +879,29 @@ std::vector<torch::Tensor> conv_wgrad(torch::Tensor dY, torch::Tensor act,
                                       int64_t N, int64_t INH, int64_t INW,
                                       int64_t OH, int64_t OW, int64_t COUT,
                                       int64_t K) {
-    long M = N * OH * OW;
-    int cin1 = 0;
-    if (conv_id == 1) {
-        TORCH_CHECK((OH - 1) * 4 + 8 <= INH && (OW - 1) * 4 + 8 <= INW,
-                    "conv_wgrad: conv1 output extent exceeds the input");
-        cin1 = conv1_cin(in, N, INH, INW, 4, 8, "conv_wgrad");
-        TORCH_CHECK(K == 64 * cin1 && COUT == 32,
-                    "conv_wgrad: conv1 expects COUT 32 and K = 64 * CIN = ",
-                    64 * cin1, ", got COUT ", COUT, " K ", K);
-        TORCH_CHECK(dY.numel() == M * COUT && act.numel() == dY.numel(),
-                    "conv_wgrad: conv1 dY/act must be (N*OH*OW, 32)");
-    }
-    auto dWt = torch::zeros({COUT, K}, dY.options().dtype(torch::kFloat32));
-    auto db = torch::zeros({COUT}, dY.options().dtype(torch::kFloat32));
-    long target_chunks = 1024;
-    long rows_per_chunk = std::max(32L, (M + target_chunks - 1) / target_chunks);
-    rows_per_chunk = ((rows_per_chunk + 31) / 32) * 32;
-    dim3 grid(ccdiv(M, rows_per_chunk));
-    auto stream = at::cuda::getCurrentCUDAStream();
-    auto* dy = reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr());
-    auto* ac = reinterpret_cast<const __hip_bfloat16*>(act.data_ptr());
-    const void* x = in.data_ptr();
-#define WLAUNCH(U8, KH_, KW_, CIN_, S_, NCOT_)                                 \
-    hipLaunchKernelGGL((conv_wgrad_kernel<U8, KH_, KW_, CIN_, S_, NCOT_,       \
-                                          true>),                              \
-                       grid, dim3(256), 0, stream.stream(), dy, ac, x,         \
-                       dWt.data_ptr<float>(), db.data_ptr<float>(), (int)M,    \
-                       (int)INH, (int)INW, (int)OH, (int)OW, (int)COUT,        \
-                       (int)rows_per_chunk)
-    if (conv_id == 1 && cin1 == 1) WLAUNCH(true, 8, 8, 1, 4, 1);
-    else if (conv_id == 1) WLAUNCH(true, 8, 8, 4, 4, 1);
-    else if (conv_id == 2) WLAUNCH(false, 4, 4, 32, 2, 2);
-    else if (conv_id == 3) WLAUNCH(false, 3, 3, 64, 1, 2);
-    else TORCH_CHECK(false, "unknown conv_id");
-#undef WLAUNCH
+    const char* who = "conv_wgrad";
+    torch::Tensor dWt, db;
+    int cin1 = conv1_cin(conv_id, in, N, 4, 8, who);
+    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        check_geometry<G>(INH, INW, OH, OW, COUT, K, who);
+        check_input<G>(in, N, who);
+        check_grads<G>(dY, act, N, who);
+        long M = N * G::NPIX;
+        dWt =
+            torch::zeros({G::COUT, G::K}, dY.options().dtype(torch::kFloat32));
+        db = torch::zeros({G::COUT}, dY.options().dtype(torch::kFloat32));
+        long target_chunks = 1024;
+        long rows_per_chunk =
+            std::max(32L, (M + target_chunks - 1) / target_chunks);
+        rows_per_chunk = ((rows_per_chunk + 31) / 32) * 32;
+        hipLaunchKernelGGL(
+            (conv_wgrad_kernel<G>), dim3(cdiv(M, rows_per_chunk)), dim3(256),
+            0, at::cuda::getCurrentCUDAStream().stream(),
+            reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+            reinterpret_cast<const __hip_bfloat16*>(act.data_ptr()),
+            in.data_ptr(), dWt.data_ptr<float>(), db.data_ptr<float>(), (int)M,
+            (int)rows_per_chunk);
+    });
     return {dWt, db};
 }

@@ -18,27 +18,6 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-union bf8u {
-    bf16x8 v;
-    uint4 u;
-    __bf16 e[8];
-};
-
-__device__ __forceinline__ bf16x8 load_bf16x8(const __hip_bfloat16* p) {
-    bf8u r;
-    r.u = *reinterpret_cast<const uint4*>(p);
-    return r.v;
-}
-
-__device__ __forceinline__ bf16x8 zero_bf16x8() {
-    bf8u r;
-    r.u = uint4{0, 0, 0, 0};
-    return r.v;
-}
-
 // ---------------------------------------------------------------------------
 // gemm_bias_act: out(M,N) = act(A(M,K) @ Wt(N,K)^T + bias)
 //   OUT_F32: write f32 (head outputs feeding the loss kernel) else bf16.
@@ -454,8 +433,6 @@ __global__ __launch_bounds__(256) void gemm_wgrad_kernel(
 // ---------------------------------------------------------------------------
 // Host wrappers
 // ---------------------------------------------------------------------------
-
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 torch::Tensor gemm_bias_act(torch::Tensor A, torch::Tensor Wt,
                             torch::Tensor bias, int64_t act, bool out_f32) {

@@ -30,29 +30,8 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-union ibf8u {
-    bf16x8 v;
-    uint4 u;
-    __bf16 e[8];
-};
-
-__device__ __forceinline__ bf16x8 iload8(const __hip_bfloat16* p) {
-    ibf8u r;
-    r.u = *reinterpret_cast<const uint4*>(p);
-    return r.v;
-}
-
-__device__ __forceinline__ bf16x8 izero() {
-    ibf8u r;
-    r.u = uint4{0, 0, 0, 0};
-    return r.v;
-}
-
 __device__ __forceinline__ bf16x8 irelu8(bf16x8 a) {
-    ibf8u r;
+    bf16x8_u r;
     r.v = a;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -146,18 +125,19 @@ __global__ __launch_bounds__(256) void conv3p_kernel(
                     a[i] = idequant8(
                         reinterpret_cast<const unsigned char*>(in) + abase[i] + off);
                 else {
-                    a[i] = iload8(
+                    a[i] = load_bf16x8(
                         reinterpret_cast<const __hip_bfloat16*>(in) + abase[i] + off);
                     if (RELU_IN) a[i] = irelu8(a[i]);
                 }
             } else {
-                a[i] = izero();
+                a[i] = zero_bf16x8();
             }
         }
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             int c = j * 16 + frow;
-            b[j] = (c < COUT && kval) ? iload8(Wt + (long)c * K + k) : izero();
+            b[j] = (c < COUT && kval) ? load_bf16x8(Wt + (long)c * K + k)
+                : zero_bf16x8();
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -242,7 +222,7 @@ __global__ __launch_bounds__(256) void conv3p_band_kernel(
                 v = idequant8(
                     reinterpret_cast<const unsigned char*>(in) + gbase + e);
             } else {
-                v = iload8(
+                v = load_bf16x8(
                     reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
                 if (RELU_IN) v = irelu8(v);
             }
@@ -259,7 +239,7 @@ __global__ __launch_bounds__(256) void conv3p_band_kernel(
         int c = wc * 16 + frow;
         int k = ki * 32 + kseg;
         wfrag[ki] = (c < COUT_T && k < K)
-                        ? iload8(Wt + (long)c * K + k) : izero();
+                        ? load_bf16x8(Wt + (long)c * K + k) : zero_bf16x8();
     }
     __syncthreads();
 
@@ -287,8 +267,8 @@ __global__ __launch_bounds__(256) void conv3p_band_kernel(
             bf16x8 a[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                a[i] = (lval[i] && kval) ? iload8(&s_in[lbase[i] + off])
-                                         : izero();
+                a[i] = (lval[i] && kval) ? load_bf16x8(&s_in[lbase[i] + off])
+                                         : zero_bf16x8();
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -371,7 +351,7 @@ __global__ __launch_bounds__(256) void conv3p_pool_band_kernel(
                 v = idequant8(
                     reinterpret_cast<const unsigned char*>(in) + gbase + e);
             else
-                v = iload8(
+                v = load_bf16x8(
                     reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
             *reinterpret_cast<bf16x8*>(&s_in[e]) = v;
         }
@@ -386,7 +366,7 @@ __global__ __launch_bounds__(256) void conv3p_pool_band_kernel(
         int c = wc * 16 + frow;
         int k = ki * 32 + kseg;
         wfrag[ki] = (c < COUT_T && k < K)
-                        ? iload8(Wt + (long)c * K + k) : izero();
+                        ? load_bf16x8(Wt + (long)c * K + k) : zero_bf16x8();
     }
     __syncthreads();
 
@@ -413,8 +393,8 @@ __global__ __launch_bounds__(256) void conv3p_pool_band_kernel(
             bf16x8 a[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                a[i] = (lval[i] && kval) ? iload8(&s_in[lbase[i] + off])
-                                         : izero();
+                a[i] = (lval[i] && kval) ? load_bf16x8(&s_in[lbase[i] + off])
+                                         : zero_bf16x8();
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -471,7 +451,7 @@ __global__ __launch_bounds__(256) void conv3p_pool_band_kernel(
                 }
             }
             constexpr int POW_ = POUT + 2, POH_ = POUT + 2;
-            ibf8u o;
+            bf16x8_u o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o.e[e] = f2bf(best[e]);
             *reinterpret_cast<bf16x8*>(
@@ -537,13 +517,13 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_kernel(
                 int mrow = t / 4;
                 int col = (t % 4) * 8;
                 long gm = m0 + mrow;
-                bf16x8 v = izero();
+                bf16x8 v = zero_bf16x8();
                 if (gm < mend) {
                     unsigned n = (unsigned)gm / (unsigned)(Hc * Wc);
                     unsigned p = (unsigned)gm % (unsigned)(Hc * Wc);
                     int oy = p / (unsigned)Wc, ox = p % (unsigned)Wc;
                     long base = (((long)n * PH + oy + 1) * PW + ox + 1) * COUT;
-                    ibf8u u;
+                    bf16x8_u u;
 #pragma unroll
                     for (int e = 0; e < 8; ++e)
                         u.e[e] = (col + e < COUT)
@@ -557,7 +537,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_kernel(
                 int mrow = e8 / (K / 8);
                 int k = (e8 % (K / 8)) * 8;
                 long gm = m0 + mrow;
-                bf16x8 w = izero();
+                bf16x8 w = zero_bf16x8();
                 if (gm < mend) {
                     unsigned n = (unsigned)gm / (unsigned)(Hc * Wc);
                     unsigned p = (unsigned)gm % (unsigned)(Hc * Wc);
@@ -569,7 +549,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_kernel(
                         w = idequant8(
                             reinterpret_cast<const unsigned char*>(in) + off);
                     else {
-                        w = iload8(
+                        w = load_bf16x8(
                             reinterpret_cast<const __hip_bfloat16*>(in) + off);
                         if (RELU_IN) w = irelu8(w);
                     }
@@ -592,7 +572,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_kernel(
             if (kcol0 + 16 <= K) {
                 fb = lds_col_frag8<K + 8>(&s_a[0][0], mbase, kcol0, lane);
             } else {
-                fb = izero();
+                fb = zero_bf16x8();
                 int kcol = kcol0 + frow;
                 if (kcol < K) {
 #pragma unroll
@@ -691,7 +671,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_tap_kernel(
                     v = idequant8(
                         reinterpret_cast<const unsigned char*>(in) + gbase + e);
                 else {
-                    v = iload8(
+                    v = load_bf16x8(
                         reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
                     if (RELU_IN) v = irelu8(v);
                 }
@@ -707,10 +687,10 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_tap_kernel(
                     int mrow = t / (COUT / 8);
                     int col = (t % (COUT / 8)) * 8;
                     int pp = p0 + mrow;
-                    bf16x8 v = izero();
+                    bf16x8 v = zero_bf16x8();
                     if (pp < npix) {
                         int yl = pp / HT, x = pp % HT;
-                        v = iload8(dY + ((n * PH + y0 + yl + 1) * (long)PW
+                        v = load_bf16x8(dY + ((n * PH + y0 + yl + 1) * (long)PW
                                          + x + 1) * COUT + col);
                     }
                     *reinterpret_cast<bf16x8*>(&s_dy[mrow][col]) = v;
@@ -743,20 +723,20 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_tap_kernel(
                 const int dy_ = tt / 3, dx_ = tt % 3;
 #pragma unroll
                 for (int c1 = 0; c1 < NCI; ++c1) {
-                    auto* p1 = (__attribute__((address_space(3))) cmn_bf16x4*)
+                    auto* p1 = (__attribute__((address_space(3))) bf16x4*)
                         &s_in[((yl1 + dy_) * PW + x1 + dx_) * CIN
                               + c1 * 16 + pc];
-                    auto* p2 = (__attribute__((address_space(3))) cmn_bf16x4*)
+                    auto* p2 = (__attribute__((address_space(3))) bf16x4*)
                         &s_in[((yl2 + dy_) * PW + x2 + dx_) * CIN
                               + c1 * 16 + pc];
                     union {
-                        struct { cmn_bf16x4 lo, hi; } p;
+                        struct { bf16x4 lo, hi; } p;
                         bf16x8 v;
                     } u;
                     u.p.lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
                     u.p.hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p2);
                     bf16x8 b = u.v;
-                    if (CIN < 16 && i15 >= CIN) b = izero();
+                    if (CIN < 16 && i15 >= CIN) b = zero_bf16x8();
 #pragma unroll
                     for (int c2 = 0; c2 < NCO; ++c2)
                         acc[ti][c2][c1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -857,7 +837,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_band_kernel(
                     v = idequant8(
                         reinterpret_cast<const unsigned char*>(in) + gbase + e);
                 } else {
-                    v = iload8(
+                    v = load_bf16x8(
                         reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
                     if (RELU_IN) v = irelu8(v);
                 }
@@ -873,12 +853,12 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_band_kernel(
                     int mrow = t / 4;
                     int col = (t % 4) * 8;
                     int pp = t0 + mrow;
-                    bf16x8 v = izero();
+                    bf16x8 v = zero_bf16x8();
                     if (pp < npix) {
                         int yl = pp / HT, x = pp % HT;
                         long base = ((n * PH + y0 + yl + 1) * (long)PW + x + 1)
                                         * COUT_T;
-                        ibf8u u;
+                        bf16x8_u u;
 #pragma unroll
                         for (int e = 0; e < 8; ++e)
                             u.e[e] = (col + e < COUT_T)
@@ -893,11 +873,12 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_band_kernel(
                     int mrow = e8 / (K / 8);
                     int k = (e8 % (K / 8)) * 8;
                     int pp = t0 + mrow;
-                    bf16x8 w = izero();
+                    bf16x8 w = zero_bf16x8();
                     if (pp < npix) {
                         int yl = pp / HT, x = pp % HT;
                         int dy_ = k / KROW, rem = k % KROW;
-                        w = iload8(&s_slab[((yl + dy_) * PW + x) * CIN + rem]);
+                        w =
+                            load_bf16x8(&s_slab[((yl + dy_) * PW + x) * CIN + rem]);
                     }
                     *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
                 }
@@ -918,7 +899,7 @@ __global__ __launch_bounds__(256) void conv3p_wgrad_band_kernel(
                 if (kcol0 + 16 <= K) {
                     fb = lds_col_frag8<K + 8>(&s_a[0][0], mbase, kcol0, lane);
                 } else {
-                    fb = izero();
+                    fb = zero_bf16x8();
                     int kcol = kcol0 + frow;
                     if (kcol < K) {
 #pragma unroll
@@ -999,8 +980,9 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(
         for (int kx = 0; kx < 3; ++kx) {
             int x = 2 * ox - 1 + kx;
             if (x < 0 || x >= W) continue;
-            ibf8u v;
-            v.v = iload8(in + (((long)n * PH + y + 1) * PW + x + 1) * C + c8 * 8);
+            bf16x8_u v;
+            v.v =
+                load_bf16x8(in + (((long)n * PH + y + 1) * PW + x + 1) * C + c8 * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float f = bf2f(v.e[e]);
@@ -1009,7 +991,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(
         }
     }
     const int POW = OW + 2, POH = OH + 2;
-    ibf8u o;
+    bf16x8_u o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o.e[e] = f2bf(best[e]);
     *reinterpret_cast<bf16x8*>(
@@ -1059,14 +1041,15 @@ __global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(
             if (kx < 0 || kx > 2) continue;
             int tap = ky * 3 + kx;
             long abase = (((long)n * OH + oy) * OW + ox) * C + c8 * 8;
-            ibf8u g;
-            g.v = iload8(dOut + (((long)n * POH + oy + 1) * POW + ox + 1) * C + c8 * 8);
+            bf16x8_u g;
+            g.v =
+                load_bf16x8(dOut + (((long)n * POH + oy + 1) * POW + ox + 1) * C + c8 * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 if (arg[abase + e] == tap) acc[e] += bf2f(g.e[e]);
         }
     }
-    ibf8u o;
+    bf16x8_u o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o.e[e] = f2bf(acc[e]);
     *reinterpret_cast<bf16x8*>(
@@ -1112,7 +1095,8 @@ __global__ __launch_bounds__(256) void pad2dense_kernel(
     t /= (unsigned)W;
     int y = (int)(t % (unsigned)H);
     unsigned n = t / (unsigned)H;
-    bf16x8 v = iload8(in + (((long)n * (H + 2) + y + 1) * (long)(W + 2) + x + 1) * C + c);
+    bf16x8 v =
+        load_bf16x8(in + (((long)n * (H + 2) + y + 1) * (long)(W + 2) + x + 1) * C + c);
     if (relu) v = irelu8(v);
     *reinterpret_cast<bf16x8*>(out + idx) = v;
 }
@@ -1130,9 +1114,9 @@ __global__ __launch_bounds__(256) void dense2pad_mask_kernel(
     int y = (int)(t % (unsigned)H);
     unsigned n = t / (unsigned)H;
     long pidx = (((long)n * (H + 2) + y + 1) * (long)(W + 2) + x + 1) * C + c;
-    ibf8u g, a, o;
-    g.v = iload8(dflat + idx);
-    a.v = iload8(act_pad + pidx);
+    bf16x8_u g, a, o;
+    g.v = load_bf16x8(dflat + idx);
+    a.v = load_bf16x8(act_pad + pidx);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
         o.e[e] = (bf2f(a.e[e]) > 0.f) ? g.e[e] : (__bf16)0.f;
@@ -1142,8 +1126,6 @@ __global__ __launch_bounds__(256) void dense2pad_mask_kernel(
 // ---------------------------------------------------------------------------
 // Host wrappers
 // ---------------------------------------------------------------------------
-
-static inline int icdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // fused stage conv + maxpool: in (padded) -> pooled out (padded) + argmax;
 // the full-resolution conv output stays in LDS.  stage: 0/1/2 selects the
@@ -1190,7 +1172,7 @@ void conv3p(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
     long CIN = in.size(3);
     long COUT = Wt.size(0) ;
     bool u8 = in.dtype() == torch::kUInt8;
-    dim3 grid(icdiv(M, 128));
+    dim3 grid(cdiv(M, 128));
     auto stream = at::cuda::getCurrentCUDAStream();
     const void* x = in.data_ptr();
     auto* w = reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr());
@@ -1302,7 +1284,7 @@ std::vector<torch::Tensor> conv3p_wgrad(torch::Tensor dY, torch::Tensor in,
     long target_chunks = 1024;
     long rows_per_chunk = std::max(64L, (M + target_chunks - 1) / target_chunks);
     rows_per_chunk = ((rows_per_chunk + 63) / 64) * 64;
-    dim3 grid(icdiv(M, rows_per_chunk));
+    dim3 grid(cdiv(M, rows_per_chunk));
     auto stream = at::cuda::getCurrentCUDAStream();
     auto* dy = reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr());
     const void* x = in.data_ptr();
@@ -1320,7 +1302,7 @@ std::vector<torch::Tensor> conv3p_wgrad(torch::Tensor dY, torch::Tensor in,
         long bpw = std::max(1L, (tb + 1023) / 1024);                          \
         hipLaunchKernelGGL((conv3p_wgrad_band_kernel<U8, CIN_, CO_, HT_,      \
                                                      TH_, RELU_>),            \
-                           dim3(icdiv(tb, bpw)), dim3(256), 0,                \
+                           dim3(cdiv(tb, bpw)), dim3(256), 0,                \
                            stream.stream(), dy, x, dWt.data_ptr<float>(),     \
                            db.data_ptr<float>(), (int)N, (int)bpw);           \
     } while (0)
@@ -1336,7 +1318,7 @@ std::vector<torch::Tensor> conv3p_wgrad(torch::Tensor dY, torch::Tensor in,
         long bpw = std::max(1L, (tb + 1023) / 1024);                          \
         hipLaunchKernelGGL((conv3p_wgrad_tap_kernel<U8, CIN_, CO_, HT_,       \
                                                     TH_, RELU_>),             \
-                           dim3(icdiv(tb, bpw)), dim3(256), 0,                \
+                           dim3(cdiv(tb, bpw)), dim3(256), 0,                \
                            stream.stream(), dy, x, dWt.data_ptr<float>(),     \
                            db.data_ptr<float>(), (int)N, (int)bpw);           \
     } while (0)
@@ -1413,7 +1395,7 @@ void maxpool3s2_fwd(torch::Tensor in, torch::Tensor out, torch::Tensor arg,
     auto stream = at::cuda::getCurrentCUDAStream();
 #define MPF(HT_, CT_)                                                         \
     hipLaunchKernelGGL((maxpool3s2_fwd_kernel<HT_, CT_>),                     \
-                       dim3(icdiv(total, 256)), dim3(256), 0,                 \
+                       dim3(cdiv(total, 256)), dim3(256), 0,                 \
                        stream.stream(),                                       \
                        reinterpret_cast<const __hip_bfloat16*>(in.data_ptr()),\
                        reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),     \
@@ -1433,7 +1415,7 @@ void maxpool3s2_bwd(torch::Tensor dOut, torch::Tensor arg, torch::Tensor dIn,
     auto stream = at::cuda::getCurrentCUDAStream();
 #define MPB(HT_, CT_)                                                         \
     hipLaunchKernelGGL((maxpool3s2_bwd_kernel<HT_, CT_>),                     \
-                       dim3(icdiv(total, 256)), dim3(256), 0,                 \
+                       dim3(cdiv(total, 256)), dim3(256), 0,                 \
                        stream.stream(),                                       \
                        reinterpret_cast<const __hip_bfloat16*>(dOut.data_ptr()),\
                        arg.data_ptr<unsigned char>(),                         \
@@ -1454,7 +1436,7 @@ void pack_frames(torch::Tensor frames, torch::Tensor out, int64_t H,
     TORCH_CHECK(out.size(1) == H + 2 && out.size(3) == 8);
     long total = M * H * W;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(pack_frames_kernel, dim3(icdiv(total, 256)), dim3(256),
+    hipLaunchKernelGGL(pack_frames_kernel, dim3(cdiv(total, 256)), dim3(256),
                        0, stream.stream(),
                        frames.data_ptr<unsigned char>(),
                        out.data_ptr<unsigned char>(), total, (int)H, (int)W,
@@ -1468,7 +1450,7 @@ torch::Tensor pad2dense(torch::Tensor in, int64_t N, int64_t H, int64_t W,
                             in.options().dtype(torch::kBFloat16));
     long total = N * H * W * C;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(pad2dense_kernel, dim3(icdiv(total / 8, 256)),
+    hipLaunchKernelGGL(pad2dense_kernel, dim3(cdiv(total / 8, 256)),
                        dim3(256), 0, stream.stream(),
                        reinterpret_cast<const __hip_bfloat16*>(in.data_ptr()),
                        reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
@@ -1481,7 +1463,7 @@ void dense2pad_mask(torch::Tensor dflat, torch::Tensor act_pad,
     long C = act_pad.size(3);
     long total = N * H * W * C;
     auto stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(dense2pad_mask_kernel, dim3(icdiv(total / 8, 256)),
+    hipLaunchKernelGGL(dense2pad_mask_kernel, dim3(cdiv(total / 8, 256)),
                        dim3(256), 0, stream.stream(),
                        reinterpret_cast<const __hip_bfloat16*>(dflat.data_ptr()),
                        reinterpret_cast<const __hip_bfloat16*>(act_pad.data_ptr()),

@@ -41,30 +41,10 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-union lbf8u {
-    bf16x8 v;
-    uint4 u;
-};
-
-__device__ __forceinline__ bf16x8 lload8(const __hip_bfloat16* p) {
-    lbf8u r;
-    r.u = *reinterpret_cast<const uint4*>(p);
-    return r.v;
-}
-
 __device__ __forceinline__ void lstore8(__hip_bfloat16* p, bf16x8 v) {
-    lbf8u r;
+    bf16x8_u r;
     r.v = v;
     *reinterpret_cast<uint4*>(p) = r.u;
-}
-
-__device__ __forceinline__ bf16x8 lzero8() {
-    lbf8u r;
-    r.u = uint4{0, 0, 0, 0};
-    return r.v;
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) {
@@ -276,7 +256,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
         int c = e / H;
         int k = e % H;
         int g = c / UNITS, j = c % UNITS;
-        lstore8(&s_whh[c][k], lload8(Whh + (long)(g * H + u0 + j) * H + k));
+        lstore8(&s_whh[c][k],
+                load_bf16x8(Whh + (long)(g * H + u0 + j) * H + k));
     }
     // h0 -> Hout[:,0] (this wg's slice); c0 -> LDS-resident cell state
     for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
@@ -315,8 +296,9 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
                 int row = e / (H / 8);
                 int k8 = (e % (H / 8)) * 8;
                 bf16x8 v = (row < Bl)
-                    ? lload8(Hout + ((long)(b0 + row) * (T + 1)) * H + base + k8)
-                    : lzero8();
+                    ? load_bf16x8(Hout + ((long)(b0 + row) * (T + 1))
+                                  * H + base + k8)
+                    : zero_bf16x8();
                 lstore8(&s_h[row][k8], v);
             }
         }
@@ -326,10 +308,11 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
         f32x4 acc[NFRAG] = {};
 #pragma unroll
         for (int k0 = 0; k0 < H; k0 += 32) {
-            bf16x8 bfr = lload8(&s_whh[wcol0 + frow][k0 + kseg]);
+            bf16x8 bfr = load_bf16x8(&s_whh[wcol0 + frow][k0 + kseg]);
 #pragma unroll
             for (int i = 0; i < NFRAG; ++i) {
-                bf16x8 afr = lload8(&s_h[wrow0 + i * 16 + frow][k0 + kseg]);
+                bf16x8 afr =
+                    load_bf16x8(&s_h[wrow0 + i * 16 + frow][k0 + kseg]);
                 acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                     afr, bfr, acc[i], 0, 0, 0);
             }
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
             if (row < Bl) {
 #pragma unroll
                 for (int j8 = 0; j8 < UNITS; j8 += 8) {
-                    bf16x8 x8 = lload8(
+                    bf16x8 x8 = load_bf16x8(
                         X + ((long)(b0 + row) * T + t) * 4 * H + g * H + u0
                         + j8);
 #pragma unroll
@@ -472,7 +455,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
     for (int e = threadIdx.x * 8; e < UNITS * 4 * H; e += blockDim.x * 8) {
         int c = e / (4 * H);
         int k = e % (4 * H);
-        lstore8(&s_wb[c][k], lload8(Whh_bwd + (long)(u0 + c) * 4 * H + k));
+        lstore8(&s_wb[c][k], load_bf16x8(Whh_bwd + (long)(u0 + c) * 4 * H + k));
     }
     for (int p = threadIdx.x; p < BROWS * UNITS; p += blockDim.x) {
         s_dh[p / UNITS][p % UNITS] = 0.f;
@@ -508,28 +491,40 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                 dgates + ((long)(b0 + arow_l) * T + t + 1) * 4 * H;
             const bool rvalid = arow_l < Bl;
             f32x4 acc = {};
-            bf16x8 a0 = rvalid ? lload8(dgrow + (c0 + 0) * 32 + kseg) : lzero8();
-            bf16x8 a1 = rvalid ? lload8(dgrow + (c0 + 1) * 32 + kseg) : lzero8();
-            bf16x8 a2 = rvalid ? lload8(dgrow + (c0 + 2) * 32 + kseg) : lzero8();
-            bf16x8 a3 = rvalid ? lload8(dgrow + (c0 + 3) * 32 + kseg) : lzero8();
+            bf16x8 a0 = rvalid ? load_bf16x8(dgrow + (c0 + 0) * 32 + kseg)
+                : zero_bf16x8();
+            bf16x8 a1 = rvalid ? load_bf16x8(dgrow + (c0 + 1) * 32 + kseg)
+                : zero_bf16x8();
+            bf16x8 a2 = rvalid ? load_bf16x8(dgrow + (c0 + 2) * 32 + kseg)
+                : zero_bf16x8();
+            bf16x8 a3 = rvalid ? load_bf16x8(dgrow + (c0 + 3) * 32 + kseg)
+                : zero_bf16x8();
 #pragma unroll 4
             for (int kc = c0; kc < cN; kc += 4) {
-                bf16x8 b0 = lload8(&s_wb[wcol0 + frow][(kc + 0) * 32 + kseg]);
-                bf16x8 b1 = lload8(&s_wb[wcol0 + frow][(kc + 1) * 32 + kseg]);
-                bf16x8 b2 = lload8(&s_wb[wcol0 + frow][(kc + 2) * 32 + kseg]);
-                bf16x8 b3 = lload8(&s_wb[wcol0 + frow][(kc + 3) * 32 + kseg]);
+                bf16x8 b0 =
+                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 0) * 32 + kseg]);
+                bf16x8 b1 =
+                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 1) * 32 + kseg]);
+                bf16x8 b2 =
+                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 2) * 32 + kseg]);
+                bf16x8 b3 =
+                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 3) * 32 + kseg]);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
                 if (kc + 4 < cN)
-                    a0 = rvalid ? lload8(dgrow + (kc + 4) * 32 + kseg) : lzero8();
+                    a0 = rvalid ? load_bf16x8(dgrow + (kc + 4) * 32 + kseg)
+                        : zero_bf16x8();
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc, 0, 0, 0);
                 if (kc + 5 < cN)
-                    a1 = rvalid ? lload8(dgrow + (kc + 5) * 32 + kseg) : lzero8();
+                    a1 = rvalid ? load_bf16x8(dgrow + (kc + 5) * 32 + kseg)
+                        : zero_bf16x8();
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc, 0, 0, 0);
                 if (kc + 6 < cN)
-                    a2 = rvalid ? lload8(dgrow + (kc + 6) * 32 + kseg) : lzero8();
+                    a2 = rvalid ? load_bf16x8(dgrow + (kc + 6) * 32 + kseg)
+                        : zero_bf16x8();
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b3, acc, 0, 0, 0);
                 if (kc + 7 < cN)
-                    a3 = rvalid ? lload8(dgrow + (kc + 7) * 32 + kseg) : lzero8();
+                    a3 = rvalid ? load_bf16x8(dgrow + (kc + 7) * 32 + kseg)
+                        : zero_bf16x8();
             }
             int ccol = lane & 15;
             int crow = (lane >> 4) * 4;
@@ -654,7 +649,7 @@ __global__ __launch_bounds__(256) void assemble_rin_kernel(
     unsigned m = idx / (unsigned)KP;
     if (k + 8 <= 512) {
         *reinterpret_cast<bf16x8*>(rin + idx) =
-            lload8(latent + (long)m * 512 + k);
+            load_bf16x8(latent + (long)m * 512 + k);
         return;
     }
     bf16x8 v;

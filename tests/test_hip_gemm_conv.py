@@ -122,67 +122,8 @@ def test_conv_fwd_matches_eager(conv_id, cin, cout, k, s, inhw):
 
 
 # -------------------------------------------------------------------------
-# Conv backward (dgrad via tap classes, wgrad)
+# Conv backward (wgrad; dgrad is further down)
 # -------------------------------------------------------------------------
-
-def test_conv3_dgrad_s1():
-    """3x3 stride-1 dgrad via padded upstream + 9 uniform taps."""
-    torch.manual_seed(3)
-    N, CIN, COUT, K, XH = 5, 64, 64, 3, 9
-    OH = XH - K + 1  # 7
-    w = (torch.randn(COUT, CIN, K, K, device="cuda") * 0.2).bfloat16()
-    x32 = torch.randn(N, CIN, XH, XH, device="cuda", requires_grad=True)
-    out = F.conv2d(x32, w.float(), stride=1)
-    dy32 = torch.randn_like(out)
-    out.backward(dy32)
-
-    dy = dy32.bfloat16()
-    pad = K - 1
-    PH = OH + 2 * pad
-    dyp = torch.zeros(N, PH, PH, COUT, device="cuda").bfloat16()
-    dyp[:, pad:pad + OH, pad:pad + OH] = dy.permute(0, 2, 3, 1)
-    # Wd[ci][t*COUT+co] = w[co, ci, dy, dx] with t = dy*K+dx ; index into
-    # dyp at (y - dy + pad) -> taps (dy, dx)
-    Wd = w.permute(1, 2, 3, 0).reshape(CIN, K * K * COUT).contiguous()
-    # reorder to (CIN, t, COUT) with t-major: already (ci, dy, dx, co) ✓
-    taps = torch.tensor([[dy, dx] for dy in range(K) for dx in range(K)],
-                        dtype=torch.int32, device="cuda")
-    dX = torch.zeros(N, XH, XH, CIN, device="cuda").bfloat16()
-    M_.conv_dgrad(dyp, Wd, taps, N, PH, PH, COUT, XH, XH, CIN, 0, 0, 1, pad, dX)
-    ref = x32.grad.permute(0, 2, 3, 1)
-    close(dX, ref, rtol=5e-2, name="conv3 dgrad")
-
-
-def test_conv2_dgrad_s2_parity_classes():
-    torch.manual_seed(2)
-    N, CIN, COUT, K, S, XH = 4, 32, 64, 4, 2, 20
-    OH = (XH - K) // S + 1  # 9
-    w = (torch.randn(COUT, CIN, K, K, device="cuda") * 0.2).bfloat16()
-    x32 = torch.randn(N, CIN, XH, XH, device="cuda", requires_grad=True)
-    out = F.conv2d(x32, w.float(), stride=S)
-    dy32 = torch.randn_like(out)
-    out.backward(dy32)
-
-    dy = dy32.bfloat16()
-    pad = 1
-    PH = OH + 2 * pad  # 11
-    dyp = torch.zeros(N, PH, PH, COUT, device="cuda").bfloat16()
-    dyp[:, pad:pad + OH, pad:pad + OH] = dy.permute(0, 2, 3, 1)
-    dX = torch.zeros(N, XH, XH, CIN, device="cuda").bfloat16()
-    w_nhwc = w.permute(0, 2, 3, 1)  # (co, dy, dx, ci)
-    for py in range(S):
-        for px in range(S):
-            tap_list = [(dy_, dx_) for dy_ in range(py, K, S)
-                        for dx_ in range(px, K, S)]
-            taps = torch.tensor(tap_list, dtype=torch.int32, device="cuda")
-            # Wd[ci][t*COUT + co] = w[co, dy_t, dx_t, ci]
-            Wd = torch.stack([w_nhwc[:, d, x_, :] for d, x_ in tap_list], dim=0)
-            Wd = Wd.permute(2, 0, 1).reshape(CIN, len(tap_list) * COUT).contiguous()
-            M_.conv_dgrad(dyp, Wd, taps, N, PH, PH, COUT, XH, XH, CIN,
-                          py, px, S, pad, dX)
-    ref = x32.grad.permute(0, 2, 3, 1)
-    close(dX, ref, rtol=5e-2, name="conv2 dgrad")
-
 
 @pytest.mark.parametrize("conv_id,cin,cout,k,s,inhw", [
     (1, 4, 32, 8, 4, 84),
@@ -228,8 +169,9 @@ def test_conv_wgrad(conv_id, cin, cout, k, s, inhw):
 # -------------------------------------------------------------------------
 
 def test_conv3_dgrad_dense_with_out_mask():
-    """Bounds-checked dense dgrad == padded-staging dgrad; the output mask
-    fuses the next conv's ReLU backward into the dX store."""
+    """3x3 stride-1 dgrad from the dense (unpadded) upstream gradient with
+    9 uniform taps, out-of-range taps dropped by a bounds check; the output
+    mask fuses the next conv's ReLU backward into the dX store."""
     torch.manual_seed(3)
     N, CIN, COUT, K, XH = 5, 64, 64, 3, 9
     OH = XH - K + 1  # 7
@@ -358,6 +300,70 @@ def test_conv_fwd_band_matches_classic(conv_id):
                       ohw, ohw, True)
     out = M_.conv_fwd_band(x_in, prepack_w(w), b, conv_id, N)
     assert torch.equal(out, ref), (out.float() - ref.float()).abs().max()
+
+
+# The band launchers pack ceil(N/2048) (fwd) / ceil(N/1024) (wgrad) images
+# per workgroup; the workload runs 3 and 6.  N just past the threshold gives
+# two images per workgroup — the second one re-stages the LDS image over
+# live data — and a ragged last workgroup.  conv3 has the smallest images;
+# conv1 with one channel has the split patch-row reads.
+_BAND_GEO = {(1, 1): (32, 8, 4, 84), (3, 64): (64, 3, 1, 9)}
+
+
+def _band_input(conv_id, cin, N, inhw):
+    if conv_id == 1:
+        return torch.randint(0, 256, (N, inhw, inhw, cin),
+                             dtype=torch.uint8, device="cuda")
+    return torch.randn(N, inhw, inhw, cin, device="cuda").bfloat16()
+
+
+@pytest.mark.parametrize("conv_id,cin", [(3, 64), (1, 1)])
+def test_conv_fwd_band_multi_image_loop(conv_id, cin):
+    cout, k, s, inhw = _BAND_GEO[(conv_id, cin)]
+    torch.manual_seed(60 + conv_id)
+    N = 2050
+    ohw = (inhw - k) // s + 1
+    w = (torch.randn(cout, cin, k, k, device="cuda") * 0.2).bfloat16()
+    b = torch.randn(cout, device="cuda") * 0.1
+    x_in = _band_input(conv_id, cin, N, inhw)
+    ref = M_.conv_fwd(x_in, prepack_w(w), b, conv_id, N, inhw, inhw,
+                      ohw, ohw, True)
+    out = M_.conv_fwd_band(x_in, prepack_w(w), b, conv_id, N)
+    assert torch.equal(out, ref), (out.float() - ref.float()).abs().max()
+
+
+@pytest.mark.parametrize("conv_id,cin", [(3, 64), (1, 1)])
+def test_conv_wgrad_band_multi_image_loop(conv_id, cin):
+    cout, k, s, inhw = _BAND_GEO[(conv_id, cin)]
+    torch.manual_seed(70 + conv_id)
+    N = 1030
+    ohw = (inhw - k) // s + 1
+    x_in = _band_input(conv_id, cin, N, inhw)
+    dY = (torch.randn(N * ohw * ohw, cout, device="cuda") * 0.5).bfloat16()
+    act = torch.randn(N * ohw * ohw, cout, device="cuda").bfloat16()
+    dWt_ref, db_ref = M_.conv_wgrad(dY, act, x_in, conv_id, N, inhw, inhw,
+                                    ohw, ohw, cout, k * k * cin)
+    dWt, db = M_.conv_wgrad_band(dY, act, x_in, conv_id, N)
+    close(dWt, dWt_ref, rtol=2e-3, atol=1e-2,
+          name=f"band wgrad {conv_id} multi-image")
+    close(db, db_ref, rtol=2e-3, atol=1e-2,
+          name=f"band bgrad {conv_id} multi-image")
+
+
+def test_conv_dgrad_dense_rejects_unsupported_geometry():
+    """Only the conv3 (9 taps, 7->9, s1) and conv2 (4 taps, 9->20, s2)
+    geometries are instantiated; anything else raises before any launch."""
+    N, CIN, COUT, K, XH, OH = 2, 64, 64, 3, 10, 7
+    dy = torch.randn(N * OH * OH, COUT, device="cuda").bfloat16()
+    Wd = torch.randn(CIN, K * K * COUT, device="cuda").bfloat16()
+    taps = torch.tensor([[dy_, dx_] for dy_ in range(K) for dx_ in range(K)],
+                        dtype=torch.int32, device="cuda")
+    dX = torch.full((N, XH, XH, CIN), 3.0, device="cuda").bfloat16()
+    with pytest.raises(RuntimeError, match="conv_dgrad_dense"):
+        M_.conv_dgrad_dense(dy, Wd, taps, torch.empty(0, device="cuda"),
+                            N, OH, OH, COUT, XH, XH, CIN, 0, 0, 1, dX)
+    torch.cuda.synchronize()
+    assert torch.equal(dX, torch.full_like(dX, 3.0))
 
 
 def test_gemm_fat_tile_matches_small():
