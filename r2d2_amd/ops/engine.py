@@ -724,16 +724,19 @@ class HipNetworkEngine:
                                    ON.taps2[(py, px)], a1,
                                    M, 9, 9, 64, 20, 20, 32, py, px, 2, d_a1)
         # conv1 wgrad (no dgrad: input is data; d_a1 pre-masked by a1).
-        # Stays on the CHUNKED kernel: measured 0.434 vs 0.474 ms for the
-        # per-image band variant (the 8x8 s4 patch field re-reads only 4x,
-        # and the band's whole-image slab costs more occupancy than the
-        # dequant re-reads save; conv2/conv3 with 9x/4x re-read DO win).
-        # One input channel (K = 64), same 5440 images: 0.242 ms chunked vs
-        # 0.241 ms band — a tie inside the chunked kernel's own round-to-
-        # round spread (0.2414-0.2444), so both channel counts share the
-        # chunked path.
-        dW1, db1 = m.conv_wgrad(d_a1.view(M * 400, 32), a1, obs_hwc, 1,
-                                M, 84, 84, 20, 20, 32, 8 * 8 * self.C)
+        # Each channel count runs the kernel measured faster for it, 5440
+        # images, device events, medians of two rounds (docs/STATUS.md):
+        # four channels (K = 256) 0.193 ms band vs 0.246-0.250 ms chunked —
+        # with the fragments gathered from the LDS image the band no longer
+        # pays an im2col copy and two barriers per 32 rows; one channel
+        # (K = 64) 0.116-0.117 ms chunked vs 0.120 ms band — the image is a
+        # quarter of the size, so there is little staging left to save.
+        if self.C == 4:
+            dW1, db1 = m.conv_wgrad_band(d_a1.view(M * 400, 32), a1,
+                                         obs_hwc, 1, M)
+        else:
+            dW1, db1 = m.conv_wgrad(d_a1.view(M * 400, 32), a1, obs_hwc, 1,
+                                    M, 84, 84, 20, 20, 32, 8 * 8 * self.C)
         self._mark("conv_bwd")
 
         enc = net.encoder

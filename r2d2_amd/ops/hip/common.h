@@ -88,20 +88,32 @@ __device__ __forceinline__ float wave_allreduce_max(float v) {
 // group's 4x16 block — semantics verified empirically on MI355X
 // (tools/tr16_probe.hip -> gpurun_out/tr16_semantics.log mode 1).
 // Requires col0 % 4 == 0 and the 16-column span in-bounds.
+//
+// lds_tr_frag8 is the gather underneath: the caller supplies this lane's two
+// piece addresses itself (lo for elements 0..3, hi for 4..7), so the rows of
+// a block need no common stride — they may be the patches of eight pixels
+// inside a staged image.  Every address must be 8-byte aligned and every
+// lane of the wave active (the read crosses lanes): pad, don't mask.
 // ---------------------------------------------------------------------------
-template <int LDE>
-__device__ __forceinline__ bf16x8 lds_col_frag8(
-    const __hip_bfloat16* s, int row0, int col0, int lane) {
-    int i15 = lane & 15;
-    auto* p = (__attribute__((address_space(3))) bf16x4*)
-        (s + (row0 + (i15 >> 2)) * LDE + col0 + 4 * (i15 & 3));
+__device__ __forceinline__ bf16x8 lds_tr_frag8(const __hip_bfloat16* lo,
+                                               const __hip_bfloat16* hi) {
+    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
     union {
         struct { bf16x4 lo, hi; } p2;
         bf16x8 v;
     } u;
-    u.p2.lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);      // rows 0..3
-    u.p2.hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p + LDE); // rows 4..7
+    u.p2.lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)lo);
+    u.p2.hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)hi);
     return u.v;
+}
+
+template <int LDE>
+__device__ __forceinline__ bf16x8 lds_col_frag8(
+    const __hip_bfloat16* s, int row0, int col0, int lane) {
+    int i15 = lane & 15;
+    const __hip_bfloat16* p =
+        s + (row0 + (i15 >> 2)) * LDE + col0 + 4 * (i15 & 3);
+    return lds_tr_frag8(p, p + 4 * LDE);        // rows 0..3, rows 4..7
 }
 
 // bf16 <-> f32 helpers ------------------------------------------------------

@@ -22,9 +22,10 @@
 //           (stride-2 convs split into parity classes so every row in a
 //           tile has the same taps; no divergence); out-of-range taps are
 //           dropped by a bounds check.
-// Wgrad:    dWt(COUT,K) += dY^T @ patch with LDS-staged 32-row tiles and
-//           f32 atomics; fused ReLU mask + bias grad; chunked (global patch
-//           reads) and band (whole image in LDS).  Both run WgradTile.
+// Wgrad:    dWt(COUT,K) += dY^T @ patch in 32-row tiles with f32 atomics;
+//           fused ReLU mask + bias grad; chunked (patch tiles copied from
+//           global memory) and band (whole image + its dY in LDS, fragments
+//           gathered straight from the image).  Both run WgradTile.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -198,9 +199,54 @@ __device__ __forceinline__ bf16x8 load_patch_row(const void* in, long off) {
         return load_bf16x8(reinterpret_cast<const __hip_bfloat16*>(in) + off);
 }
 
-// Stage image n whole into LDS (one global read + one dequant per element).
-// The caller owns the barriers around it.
+// LDS layouts of a staged image: element (y, x, c) lives at y*RS + x*PS + c.
+// DenseImage is plain NHWC.
 template <class G>
+struct DenseImage {
+    static constexpr int PS = G::CIN, RS = G::INW * G::CIN, SIZE = G::IMG;
+    __device__ __forceinline__ static int offset(int e) { return e; }
+};
+
+// GatherImage pads pixels and rows for the wgrad's transpose-read gather,
+// which reads the same 32-byte k-run of 8 consecutive OUTPUT pixels per
+// 32-lane half: the stride between output pixels, S*PS elements, is made
+// 8 * odd banks (S*PS = 16 mod 32 elements; dense conv2/conv3 have 128 B =
+// 32 banks, every other pixel on the same banks), and the row pad makes the
+// step from the last pixel of an output row to the first of the next equal
+// to that stride modulo all 64 banks (128 elements), so the 8 pixels may
+// straddle output rows.  conv1's stride (32 B with four channels, 8 B with
+// one, where a k-run is 16 B) needs no pad, and 4*84*CIN is already right.
+template <class G>
+struct GatherImage {
+    static constexpr int pixel_stride() {
+        if (G::S * G::CIN < 32) return G::CIN;
+        int ps = G::CIN;
+        while ((G::S * ps) % 32 != 16) ps += 8;
+        return ps;
+    }
+    static constexpr int PS = pixel_stride();
+    static constexpr int row_stride() {
+        int rs = G::INW * PS;
+        while ((G::S * rs - G::OW * G::S * PS) % 128 != 0) rs += 4;
+        return rs;
+    }
+    static constexpr int RS = row_stride();
+    static constexpr int SIZE = G::INH * RS;
+    static constexpr bool DENSE = PS == G::CIN && RS == G::INW * G::CIN;
+    // 8-element staging chunks stay inside a pixel and 16-byte aligned;
+    // every gathered piece (4 elements of one pixel's k-run) 8-byte aligned
+    static_assert(DENSE || (G::CIN % 8 == 0 && PS % 8 == 0 && RS % 8 == 0));
+    static_assert((G::S * PS) % 4 == 0 && RS % 4 == 0 && G::KWC % 4 == 0);
+    __device__ __forceinline__ static int offset(int e) {
+        if constexpr (DENSE) return e;
+        int r = e % (G::INW * G::CIN);
+        return e / (G::INW * G::CIN) * RS + r / G::CIN * PS + r % G::CIN;
+    }
+};
+
+// Stage image n whole into LDS in layout L (one global read + one dequant
+// per element).  The caller owns the barriers around it.
+template <class G, class L = DenseImage<G>>
 __device__ __forceinline__ void stage_image(__hip_bfloat16* s_img,
                                             const void* in, long n) {
     const long gbase = n * G::IMG;
@@ -212,7 +258,7 @@ __device__ __forceinline__ void stage_image(__hip_bfloat16* s_img,
         else
             v = load_bf16x8(
                 reinterpret_cast<const __hip_bfloat16*>(in) + gbase + e);
-        *reinterpret_cast<bf16x8*>(&s_img[e]) = v;
+        *reinterpret_cast<bf16x8*>(&s_img[L::offset(e)]) = v;
     }
 }
 
@@ -366,34 +412,48 @@ __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
 
 // ---------------------------------------------------------------------------
 // Wgrad: dWt(COUT, K) += sum_rows relu_mask(dY)[row][co] * patch[row][k]
-// The FULL K extent (<= 576) and full COUT (<= 64) are staged per 32-row
+// The FULL K extent (<= 576) and full COUT (<= 64) are covered per 32-row
 // tile, so dY and the patches are each read exactly once; per-wave
 // accumulators cover all k-tiles and are flushed with f32 atomics once per
 // workgroup.  Fused ReLU mask + bias grad.
 //
 // WgradTile is everything the chunked and the band kernel share: the wave
-// split, the accumulators, one 32-row tile step (stage, gather, MFMA, bias
-// column sum) and the atomic flush.  The kernels differ only in where a patch
-// row comes from (global vs the LDS image) and in their outer loop.
+// split, the accumulators, the masked dY staging, one 32-row MFMA step, the
+// bias column sum and the atomic flush.  The kernels differ only in where a
+// B fragment comes from (a patch tile copied from global memory vs a gather
+// straight out of the LDS image) and in their outer loop.
+//
+// Both operands are gathered with transpose-reads (common.h).  The 32 GEMM
+// rows of a step are dealt to the lanes in 4-row blocks so that the eight
+// rows one 32-lane half reads at a time are CONSECUTIVE: lane group g
+// (lane / 16) takes block 4*(g/2) + (g%2) with its first read and the block
+// two further on with its second, i.e. rows row_lo + {0, 8}.  Consecutive
+// rows have one stride, so a row stride of 8 * odd banks spreads a half's
+// eight 32-byte pieces over all 64 banks.
 // ---------------------------------------------------------------------------
 template <class G>
 struct WgradTile {
     static constexpr int K = G::K, COUT = G::COUT;
     // NCOT = co tiles of 32 (1 when COUT<=32): waves split K 4/NCOT ways so
     // no wave computes guarded-away co columns
-    static constexpr int NCOT = (COUT + 31) / 32;
+    static constexpr int NCOT = COUT / 32;
     static constexpr int NKW = 4 / NCOT;              // k splits
-    // per-wave k extent, in whole 16-col fragments (K = 64, the one-channel
-    // conv1, gives each of the 4 waves exactly one fragment)
-    static constexpr int KHALF = ((K / NKW + 15) / 16) * 16;
+    static constexpr int KHALF = K / NKW;             // per-wave k extent
     static constexpr int KFRAG = KHALF / 16;          // 16-col frags per wave
-    static constexpr int LD_DY = 64 + 8, LD_A = K + 8;   // padded LDS rows
-    typedef __hip_bfloat16 DyTile[32][LD_DY];
+    static_assert(COUT % 32 == 0 && 256 % COUT == 0 && KHALF % 16 == 0,
+                  "waves own whole 32-co tiles and whole 16-column k frags");
+    // padded LDS rows, in elements: 96 B / 160 B for dY and K*2 + 32 B for
+    // the patch tile are all 8 * odd banks (see above) and keep 16-byte rows
+    static constexpr int LD_DY = COUT + 16, LD_A = K + 16;
+    static_assert((LD_DY / 2) % 16 == 8 && (LD_A / 2) % 16 == 8,
+                  "row strides of 8 * odd banks");
     typedef __hip_bfloat16 PatchTile[32][LD_A];
 
     int lane;
     int wr;     // co tile
     int wc;     // k split
+    int row_lo; // tile row of this lane's first piece; the second is 8 on
+    int pcol;   // column of the piece inside a 16-column fragment
     // co extent per wave is always 32 (2 fragments of 16)
     f32x4 acc[2][KFRAG] = {};
     float bias_acc = 0.f;
@@ -403,94 +463,97 @@ struct WgradTile {
         lane = threadIdx.x & (WAVE - 1);
         wr = (NCOT == 1) ? 0 : (wave >> 1);
         wc = (NCOT == 1) ? wave : (wave & 1);
+        int g = lane >> 4, i15 = lane & 15;
+        row_lo = 16 * (g >> 1) + 4 * (g & 1) + (i15 >> 2);
+        pcol = 4 * (i15 & 3);
     }
 
-    // One tile step over GEMM rows gm0 .. gm0+31, of which the first nvalid
-    // exist (the rest stage as zero).  patch_row(mrow, k) returns the 8 patch
-    // elements k..k+7 of row gm0 + mrow; it is only called for mrow < nvalid.
-    template <class PatchRow>
-    __device__ __forceinline__ void accumulate(
-        DyTile& s_dy, PatchTile& s_a,
+    // first k column of this lane's piece of the wave's kf-th fragment
+    __device__ __forceinline__ int frag_k(int kf) const {
+        return wc * KHALF + kf * 16 + pcol;
+    }
+
+    // Stage `rows` rows of dY, masked by the forward output's ReLU, with
+    // 16-byte loads: GEMM rows gm0 .. gm0+nvalid-1, zero rows after them.
+    // The caller owns the barriers around it.
+    __device__ __forceinline__ static void stage_dy(
+        __hip_bfloat16* s_dy,                    // [rows][LD_DY]
         const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
         const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward output
-        long gm0, int nvalid, PatchRow&& patch_row) {
-        __syncthreads();
-        int t = threadIdx.x;
-        {   // dY rows, masked by the forward output's ReLU
-            int mrow = t / 8;
-            int col = (t % 8) * 8;
-            long gm = gm0 + mrow;
+        long gm0, int nvalid, int rows) {
+        constexpr int C8 = COUT / 8;
+        for (int e8 = threadIdx.x; e8 < rows * C8; e8 += 256) {
+            int mrow = e8 / C8;
+            int col = (e8 % C8) * 8;
             bf16x8 v = zero_bf16x8();
             if (mrow < nvalid) {
+                long off = (gm0 + mrow) * COUT + col;
+                bf16x8 g = load_bf16x8(dY + off);
+                bf16x8 m = load_bf16x8(act + off);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    int c = col + e;
-                    float g = (c < COUT) ? bf2f(dY[gm * COUT + c]) : 0.f;
-                    float m_ = (c < COUT) ? bf2f(act[gm * COUT + c]) : 0.f;
-                    v[e] = (__bf16)((m_ > 0.f) ? g : 0.f);
-                }
+                for (int e = 0; e < 8; ++e)
+                    v[e] = ((float)m[e] > 0.f) ? g[e] : (__bf16)0.f;
             }
-            *reinterpret_cast<bf16x8*>(&s_dy[mrow][col]) = v;
+            *reinterpret_cast<bf16x8*>(&s_dy[mrow * LD_DY + col]) = v;
         }
-        for (int e8 = t; e8 < 32 * (K / 8); e8 += 256) {
-            int mrow = e8 / (K / 8);
-            int k = (e8 % (K / 8)) * 8;
-            bf16x8 w = (mrow < nvalid) ? patch_row(mrow, k) : zero_bf16x8();
-            *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
-        }
-        __syncthreads();
+    }
 
-        // fragment gathers via hardware transpose-reads (common.h)
-        int frow = lane & 15;
-        int mseg = (lane >> 4) * 8;
+    // One MFMA step over the 32 staged dY rows at s_dy.  frag_b(kf) returns
+    // the lane's B fragment of the wave's kf-th 16 k columns: elements 0..3
+    // from tile row row_lo, 4..7 from row_lo + 8, piece column frag_k(kf).
+    template <class FragB>
+    __device__ __forceinline__ void mma(const __hip_bfloat16* s_dy,
+                                        FragB&& frag_b) {
         bf16x8 fa[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-            fa[i] = lds_col_frag8<LD_DY>(&s_dy[0][0], mseg,
-                                         wr * 32 + i * 16, lane);
+        for (int i = 0; i < 2; ++i) {
+            const __hip_bfloat16* p =
+                s_dy + row_lo * LD_DY + wr * 32 + i * 16 + pcol;
+            fa[i] = lds_tr_frag8(p, p + 8 * LD_DY);
+        }
 #pragma unroll
         for (int kf = 0; kf < KFRAG; ++kf) {
-            int kcol0 = wc * KHALF + kf * 16;
-            bf16x8 fb;
-            if (kcol0 + 16 <= K) {
-                fb = lds_col_frag8<LD_A>(&s_a[0][0], mseg, kcol0, lane);
-            } else {                       // partial tail column span
-                fb = zero_bf16x8();
-                int kcol = kcol0 + frow;
-                if (kcol < K) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        fb[e] = *(const __bf16*)&s_a[mseg + e][kcol];
-                }
-            }
+            bf16x8 fb = frag_b(kf);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 acc[i][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                     fa[i], fb, acc[i][kf], 0, 0, 0);
         }
-
-        if (threadIdx.x < 64) {
-            int c = threadIdx.x;
-            for (int mr = 0; mr < 32; ++mr) bias_acc += bf2f(s_dy[mr][c]);
-        }
     }
 
+    // bias grad: column sums of `rows` staged rows, 256 / COUT threads each
+    __device__ __forceinline__ void bias_rows(const __hip_bfloat16* s_dy,
+                                              int rows) {
+        int c = threadIdx.x % COUT;
+        for (int mr = threadIdx.x / COUT; mr < rows; mr += 256 / COUT)
+            bias_acc += bf2f(s_dy[mr * LD_DY + c]);
+    }
+
+    // s_red: 256 floats of LDS that nothing else uses any more.  The bias
+    // partials of a column are summed there first: one atomic per column
+    // and workgroup (all workgroups hit the same COUT addresses).
     __device__ __forceinline__ void flush(float* __restrict__ dWt,  // (COUT, K)
-                                          float* __restrict__ db) { // (COUT,)
+                                          float* __restrict__ db,   // (COUT,)
+                                          float* s_red) {
         for_each_acc(acc, lane, [&](int r, int c, float v) {
             long co = wr * 32 + r;
             long kk = wc * KHALF + c;
-            if (co < COUT && kk < K) atomicAdd(&dWt[co * K + kk], v);
+            atomicAdd(&dWt[co * K + kk], v);
         });
-        if (threadIdx.x < 64) {
-            long c = threadIdx.x;
-            if (c < COUT) atomicAdd(&db[c], bias_acc);
+        __syncthreads();
+        s_red[threadIdx.x] = bias_acc;
+        __syncthreads();
+        if (threadIdx.x < COUT) {
+            float s = 0.f;
+            for (int i = threadIdx.x; i < 256; i += COUT) s += s_red[i];
+            atomicAdd(&db[threadIdx.x], s);
         }
     }
 };
 
-// chunked wgrad: a workgroup owns rows_per_chunk GEMM rows; patch rows are
-// read from the global image.
+// chunked wgrad: a workgroup owns rows_per_chunk GEMM rows; each 32-row tile
+// of patches is copied from the global image into s_a, one barrier pair per
+// tile.
 template <class G>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
@@ -499,21 +562,39 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     float* __restrict__ dWt,                 // (COUT, K) f32
     float* __restrict__ db,                  // (COUT,) f32
     int M, int rows_per_chunk) {
-    __shared__ typename WgradTile<G>::DyTile s_dy;
-    __shared__ typename WgradTile<G>::PatchTile s_a;
-    WgradTile<G> tile;
+    using Tile = WgradTile<G>;
+    constexpr int K = G::K;
+    __shared__ __attribute__((aligned(16)))
+        __hip_bfloat16 s_dy[32 * Tile::LD_DY];
+    __shared__ __attribute__((aligned(16))) typename Tile::PatchTile s_a;
+    Tile tile;
     long mstart = (long)blockIdx.x * rows_per_chunk;
     long mend = min((long)M, mstart + rows_per_chunk);
 
-    for (long m0 = mstart; m0 < mend; m0 += 32)
-        tile.accumulate(s_dy, s_a, dY, act, m0, (int)min(32L, mend - m0),
-                        [&](int mrow, int k) {
-            long base = patch_origin<G>((unsigned)(m0 + mrow));
-            int dy_ = k / G::KWC, rem = k % G::KWC;
-            return load_patch_row<G>(
-                in, base + (long)dy_ * G::INW * G::CIN + rem);
+    for (long m0 = mstart; m0 < mend; m0 += 32) {
+        int nvalid = (int)min(32L, mend - m0);
+        __syncthreads();
+        Tile::stage_dy(s_dy, dY, act, m0, nvalid, 32);
+        for (int e8 = threadIdx.x; e8 < 32 * (K / 8); e8 += 256) {
+            int mrow = e8 / (K / 8);
+            int k = (e8 % (K / 8)) * 8;
+            bf16x8 w = zero_bf16x8();
+            if (mrow < nvalid) {
+                long base = patch_origin<G>((unsigned)(m0 + mrow));
+                int dy_ = k / G::KWC, rem = k % G::KWC;
+                w = load_patch_row<G>(
+                    in, base + (long)dy_ * G::INW * G::CIN + rem);
+            }
+            *reinterpret_cast<bf16x8*>(&s_a[mrow][k]) = w;
+        }
+        __syncthreads();
+        tile.mma(s_dy, [&](int kf) {
+            const __hip_bfloat16* p = &s_a[tile.row_lo][tile.frag_k(kf)];
+            return lds_tr_frag8(p, p + 8 * Tile::LD_A);
         });
-    tile.flush(dWt, db);
+        tile.bias_rows(s_dy, 32);
+    }
+    tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
 }
 
 // ---------------------------------------------------------------------------
@@ -604,12 +685,19 @@ __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
 // ---------------------------------------------------------------------------
 // conv_wgrad_band: per-image wgrad.  The WHOLE input image fits in LDS for
 // every Nature-CNN conv (conv1 84x84x4 u8->bf16 56 KB, conv2 20x20x32
-// 26 KB, conv3 9x9x64 10 KB), so one workgroup stages it ONCE (single
-// dequant per input element instead of one per patch overlap), rebuilds
-// each 32-row patch tile LDS->LDS, and accumulates its images' whole
-// contribution in registers with ONE atomic flush at the end.  Replaces
-// conv_wgrad_kernel's global patch re-reads (conv1: 557 MB -> 154 MB per
-// step).
+// 26 KB, conv3 9x9x64 10 KB), and so does the image's whole masked dY
+// (rounded up to a multiple of 32 zero rows: 39 / 15 / 10 KB; four-channel
+// conv1 takes it in two halves, see ROWS).  A workgroup
+// stages both ONCE per image (single dequant per input element instead of
+// one per patch overlap; conv1: 557 MB -> 154 MB per step) and then runs
+// the image's 32-row tiles with no barrier between them: the B fragments
+// are gathered straight out of the image — tile row q of a fragment is the
+// patch of output pixel p0 + q, a transpose-read takes one address per lane,
+// and a lane's 4 k-elements lie inside one kernel row (KWC % 4 == 0) — so
+// no im2col tile is ever written.  Rows past the image's last pixel gather
+// that last pixel against zero dY rows (pad, don't mask: the read needs
+// every lane active).  Each image's contribution accumulates in registers,
+// with ONE atomic flush per workgroup.
 // ---------------------------------------------------------------------------
 template <class G>
 __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
@@ -619,32 +707,59 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
     float* __restrict__ dWt,                 // (COUT, K) f32
     float* __restrict__ db,                  // (COUT,) f32
     int N, int imgs_per_wg) {
+    using Tile = WgradTile<G>;
+    using Img = GatherImage<G>;
     constexpr int NPIX = G::NPIX;
-    __shared__ __hip_bfloat16 s_img[G::IMG];
-    __shared__ typename WgradTile<G>::DyTile s_dy;
-    __shared__ typename WgradTile<G>::PatchTile s_a;
-    WgradTile<G> tile;
+    // dY rows staged at a time: the whole image, except where image + dY
+    // would pass half a CU's 160 KB of LDS (conv1 with four channels, 94 KB)
+    // and leave one workgroup per CU with nothing to overlap its staging
+    // with; there dY goes in two halves of 7 tiles (76 KB)
+    constexpr int TILES = (NPIX + 31) / 32;
+    constexpr bool WHOLE =
+        (Img::SIZE + TILES * 32 * Tile::LD_DY) * 2 <= 80 * 1024;
+    constexpr int ROWS = (WHOLE ? TILES : (TILES + 1) / 2) * 32;
+    static_assert((Img::SIZE + ROWS * Tile::LD_DY) * 2 <= 80 * 1024);
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_img[Img::SIZE];
+    __shared__ __attribute__((aligned(16)))
+        __hip_bfloat16 s_dy[ROWS * Tile::LD_DY];
+    Tile tile;
+
+    // image offset of this lane's piece of each k fragment, from the patch
+    // origin: k = (dy, kx, c)
+    int koff[Tile::KFRAG];
+#pragma unroll
+    for (int kf = 0; kf < Tile::KFRAG; ++kf) {
+        int k = tile.frag_k(kf);
+        int rem = k % G::KWC;
+        koff[kf] = k / G::KWC * Img::RS + rem / G::CIN * Img::PS
+                   + rem % G::CIN;
+    }
+    // patch origin of output pixel pp, clamped into the image
+    auto origin = [](int pp) {
+        pp = min(pp, NPIX - 1);
+        return (pp / G::OW * Img::RS + pp % G::OW * Img::PS) * G::S;
+    };
 
     const long n0 = (long)blockIdx.x * imgs_per_wg;
     const long n1 = min((long)N, n0 + imgs_per_wg);
     for (long n = n0; n < n1; ++n) {
-        // s_img is read only while a patch tile is staged, i.e. before
-        // accumulate()'s second barrier; this one keeps the restage behind
-        // the previous image's last tile as a whole
-        __syncthreads();
-        stage_image<G>(s_img, in, n);
-        for (int p0 = 0; p0 < NPIX; p0 += 32)
-            tile.accumulate(s_dy, s_a, dY, act, n * NPIX + p0, NPIX - p0,
-                            [&](int mrow, int k) {
-                int pp = p0 + mrow;
-                int oy = pp / G::OW, ox = pp % G::OW;
-                int dy_ = k / G::KWC, rem = k % G::KWC;
-                return lds_patch_row<G::CIN>(
-                    &s_img[((oy * G::S + dy_) * G::INW + ox * G::S) * G::CIN
-                           + rem]);
-            });
+        for (int r0 = 0; r0 < NPIX; r0 += ROWS) {
+            __syncthreads();    // the tiles staged before are done
+            if (r0 == 0) stage_image<G, Img>(s_img, in, n);
+            Tile::stage_dy(s_dy, dY, act, n * NPIX + r0, NPIX - r0, ROWS);
+            __syncthreads();
+            tile.bias_rows(s_dy, ROWS);
+            for (int p0 = r0; p0 < min(r0 + ROWS, NPIX); p0 += 32) {
+                const __hip_bfloat16* lo = s_img + origin(p0 + tile.row_lo);
+                const __hip_bfloat16* hi =
+                    s_img + origin(p0 + tile.row_lo + 8);
+                tile.mma(s_dy + (p0 - r0) * Tile::LD_DY, [&](int kf) {
+                    return lds_tr_frag8(lo + koff[kf], hi + koff[kf]);
+                });
+            }
+        }
     }
-    tile.flush(dWt, db);
+    tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
 }
 
 // ---------------------------------------------------------------------------
@@ -712,6 +827,13 @@ static void check_grads(const torch::Tensor& dY, const torch::Tensor& act,
     TORCH_CHECK(dY.numel() == N * G::NPIX * G::COUT
                 && act.numel() == dY.numel(), who, ": dY/act must be (N*",
                 G::NPIX, ", ", G::COUT, ")");
+    // rows are staged with 16-byte loads
+    for (const torch::Tensor* t : {&dY, &act})
+        TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16
+                    && t->is_contiguous()
+                    && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                    who, ": dY/act must be contiguous, 16-byte aligned bf16 "
+                    "device tensors");
 }
 
 // the geometry arguments of the classic entry points must name the layer
@@ -861,7 +983,13 @@ std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
         dWt =
             torch::zeros({G::COUT, G::K}, dY.options().dtype(torch::kFloat32));
         db = torch::zeros({G::COUT}, dY.options().dtype(torch::kFloat32));
-        int imgs = cdiv(N, 1024);
+        // 512 workgroups = the 2 per CU that VGPRs (conv2/conv3) or LDS
+        // (conv1) allow, times 256 CUs: one resident round with no tail,
+        // and every workgroup fewer is COUT*K atomics fewer in the flush.
+        // Measured for 5440 images, 1024 / 512 / 256 workgroups: conv3
+        // 162 / 122 / 121 us, conv2 170 / 129 / 145, conv1 (4 ch) 217 / 193
+        // / 334.
+        int imgs = cdiv(N, 512);
         int grid = cdiv(N, imgs);
         hipLaunchKernelGGL(
             (conv_wgrad_band_kernel<G>), dim3(grid), dim3(256), 0,
