@@ -753,17 +753,41 @@ void handoff_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks) {
                        (int)steps, (int)nblocks);
 }
 
+// Operand checks shared by the two LSTM wrappers: every one runs BEFORE the
+// workspace reset and the launch, so a bad operand raises and nothing runs.
+static void lstm_check(const torch::Tensor& t, const char* name,
+                       c10::ScalarType dtype,
+                       std::initializer_list<int64_t> shape) {
+    TORCH_CHECK(t.defined() && t.is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t.scalar_type() == dtype, name, " must be ", dtype, ", got ",
+                t.scalar_type());
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(t.sizes() == c10::IntArrayRef(shape.begin(), shape.size()),
+                name, " must have shape ",
+                c10::IntArrayRef(shape.begin(), shape.size()), ", got ",
+                t.sizes());
+}
+
 std::vector<torch::Tensor> lstm_fwd(
     torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
     torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
     torch::Tensor barrier_ws, bool want_stash) {
     TORCH_CHECK(X0.is_cuda() && X0.dtype() == torch::kBFloat16 && X0.is_contiguous());
+    TORCH_CHECK(X0.dim() == 3, "X0 must be (B, T, 4H)");
     long B = X0.size(0), T = X0.size(1);
     long H4 = X0.size(2);
     long H = H4 / 4;
-    TORCH_CHECK(H == 512, "lstm_fwd is instantiated for H=512");
-    TORCH_CHECK(B <= 64, "B <= 64 per launch");
+    TORCH_CHECK(H4 == 2048, "lstm_fwd is instantiated for H=512");
+    TORCH_CHECK(B >= 1 && B <= 64, "1 <= B <= 64 per launch");
     bool two = X1.defined() && X1.numel() > 0;
+    lstm_check(Whh0, "Whh0", torch::kBFloat16, {H4, H});
+    lstm_check(init0, "init0", torch::kFloat32, {2, B, H});
+    lstm_check(lens, "lens", torch::kInt32, {B});
+    if (two) {
+        lstm_check(X1, "X1", torch::kBFloat16, {B, T, H4});
+        lstm_check(Whh1, "Whh1", torch::kBFloat16, {H4, H});
+        lstm_check(init1, "init1", torch::kFloat32, {2, B, H});
+    }
 
     auto bf = X0.options();
     auto f32 = X0.options().dtype(torch::kFloat32);
@@ -835,9 +859,20 @@ torch::Tensor lstm_bwd(torch::Tensor stash, torch::Tensor Cout,
                        torch::Tensor Hout, torch::Tensor dHext,
                        torch::Tensor Whh_bwd, torch::Tensor lens,
                        torch::Tensor barrier_ws) {
+    TORCH_CHECK(stash.defined() && stash.dim() == 3,
+                "stash must be (B, T, 4H)");
     long B = stash.size(0), T = stash.size(1), H4 = stash.size(2);
     long H = H4 / 4;
-    TORCH_CHECK(H == 512, "lstm_bwd is instantiated for H=512");
+    TORCH_CHECK(H4 == 2048, "lstm_bwd is instantiated for H=512");
+    // every layout below covers at most 64 rows (4 quarters of 16): rows
+    // past that would come back unwritten from torch::empty
+    TORCH_CHECK(B >= 1 && B <= 64, "1 <= B <= 64 per launch");
+    lstm_check(stash, "stash", torch::kBFloat16, {B, T, H4});
+    lstm_check(Cout, "Cout", torch::kFloat32, {B, T + 1, H});
+    lstm_check(Hout, "Hout", torch::kBFloat16, {B, T + 1, H});
+    lstm_check(dHext, "dHext", torch::kFloat32, {B, T, H});
+    lstm_check(Whh_bwd, "Whh_bwd", torch::kBFloat16, {H, H4});
+    lstm_check(lens, "lens", torch::kInt32, {B});
     auto dgates = torch::empty({B, T, H4}, stash.options());
     // Measured DEAD END (docs/KERNELS.md): 32-unit bwd slices
     // (R2D2_LSTM_BWD_UNITS=32) run 1.34 ms vs 0.94 ms at 16 — the 131 KB
