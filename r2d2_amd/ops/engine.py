@@ -245,24 +245,20 @@ class _NetPack:
             w3_nhwc = w3.permute(0, 2, 3, 1)                   # (co,dy,dx,ci)
             self.w3d = (w3_nhwc.permute(3, 1, 2, 0)            # (ci,dy,dx,co)
                         .reshape(64, 9 * 64).bfloat16().contiguous())
-            self.taps3 = torch.tensor(
-                [[dy, dx] for dy in range(3) for dx in range(3)],
-                dtype=torch.int32, device=dev)
+            # conv2 (stride 2): one (ci, tap, co) slab per parity class
+            # (py, px), at index 2*py + px of a single tensor; the class's
+            # taps are dy = py, py+2 (outer) by dx = px, px+2
             w2 = enc.conv2.weight.detach().to(dev)             # (64,32,4,4)
             w2_nhwc = w2.permute(0, 2, 3, 1)                   # (co,dy,dx,ci)
-            self.w2d = {}
-            self.taps2 = {}
+            slabs = []
             for py in range(2):
                 for px in range(2):
                     tap_list = [(dy, dx) for dy in range(py, 4, 2)
                                 for dx in range(px, 4, 2)]
                     wd = torch.stack([w2_nhwc[:, d, x, :] for d, x in tap_list],
                                      dim=0)                    # (t, co, ci)
-                    self.w2d[(py, px)] = (wd.permute(2, 0, 1)
-                                          .reshape(32, 4 * 64)
-                                          .bfloat16().contiguous())
-                    self.taps2[(py, px)] = torch.tensor(
-                        tap_list, dtype=torch.int32, device=dev)
+                    slabs.append(wd.permute(2, 0, 1).reshape(32, 4 * 64))
+            self.w2d = torch.stack(slabs).bfloat16().contiguous()  # (4,32,256)
 
 
 class HipNetworkEngine:
@@ -709,20 +705,15 @@ class HipNetworkEngine:
         # per-image band wgrads: whole input image staged in LDS once
         # (single dequant per element; conv1 patch traffic 557 -> 154 MB)
         dW3, db3 = m.conv_wgrad_band(dflat3, a3, a2, 3, M)
-        # dense bounds-checked dgrad (no zero-padded staging copies); the
-        # output mask fuses conv2's relu backward into the d_a2 store
-        d_a2 = torch.empty(M, 9, 9, 64, device=dev, dtype=torch.bfloat16)
-        m.conv_dgrad_dense(dflat3, ON.w3d, ON.taps3, a2,
-                           M, 7, 7, 64, 9, 9, 64, 0, 0, 1, d_a2)
-        # conv2 backward (d_a2 pre-masked by a2)
+        # per-image band dgrad (dY staged once in LDS inside a zero halo, no
+        # zero-padded staging copies in memory); the output mask fuses
+        # conv2's relu backward into the d_a2 store
+        d_a2 = m.conv_dgrad_band(dflat3, ON.w3d, a2, 3, M)
+        # conv2 backward (d_a2 pre-masked by a2); all four stride-parity
+        # classes of the dgrad run in the one launch
         d_a2f = d_a2.view(M * 81, 64)
         dW2, db2 = m.conv_wgrad_band(d_a2f, a2, a1, 2, M)
-        d_a1 = torch.empty(M, 20, 20, 32, device=dev, dtype=torch.bfloat16)
-        for py in range(2):
-            for px in range(2):
-                m.conv_dgrad_dense(d_a2f, ON.w2d[(py, px)],
-                                   ON.taps2[(py, px)], a1,
-                                   M, 9, 9, 64, 20, 20, 32, py, px, 2, d_a1)
+        d_a1 = m.conv_dgrad_band(d_a2f, ON.w2d, a1, 2, M)
         # conv1 wgrad (no dgrad: input is data; d_a1 pre-masked by a1).
         # Each channel count runs the kernel measured faster for it, 5440
         # images, device events, medians of two rounds (docs/STATUS.md):

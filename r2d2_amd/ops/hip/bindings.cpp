@@ -68,7 +68,11 @@ std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
                                            torch::Tensor in, int64_t conv_id,
                                            int64_t N);
 torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
-                            torch::Tensor bias, int64_t conv_id, int64_t N);
+                            torch::Tensor bias, int64_t conv_id, int64_t N,
+                            int64_t max_wgs);
+torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
+                              torch::Tensor actx, int64_t conv_id, int64_t N,
+                              int64_t max_wgs);
 
 // lstm_kernels.hip
 torch::Tensor assemble_rin(torch::Tensor latent, torch::Tensor la,
@@ -166,7 +170,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "per-image band wgrad (whole input image LDS-staged, one dequant "
           "per element, register accumulation, one atomic flush per wg)");
     m.def("conv_fwd_band", &conv_fwd_band,
-          "per-image band forward (image + weights LDS-resident)");
+          "per-image band forward (image LDS-resident; weights in LDS for "
+          "conv1, in registers for the 64-output layers)",
+          py::arg("in"), py::arg("Wt"), py::arg("bias"), py::arg("conv_id"),
+          py::arg("N"), py::arg("max_wgs") = 0);
+    m.def("conv_dgrad_band", &conv_dgrad_band,
+          "per-image band dgrad: dY staged once in LDS in a zero halo, all "
+          "parity classes in one launch, dX stored through LDS with the "
+          "optional fused output ReLU mask",
+          py::arg("dY"), py::arg("Wd"), py::arg("actx"), py::arg("conv_id"),
+          py::arg("N"), py::arg("max_wgs") = 0);
     m.def("lstm_fwd", &lstm_fwd,
           "Persistent fused LSTM forward (dual-network, length-masked)");
     m.def("lstm_bwd", &lstm_bwd, "Persistent fused LSTM BPTT backward");

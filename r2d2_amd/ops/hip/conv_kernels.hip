@@ -17,11 +17,16 @@
 // it.  Nothing else is instantiated: a call that matches no layer raises.
 //
 // Forward:  out(M=N*OH*OW, COUT) = act(patch(M,K) @ Wt^T + bias); classic
-//           (global patch reads) and band (whole image + weights in LDS).
-// Dgrad:    dX from the dense, pre-masked dY via uniform tap tables
-//           (stride-2 convs split into parity classes so every row in a
-//           tile has the same taps; no divergence); out-of-range taps are
-//           dropped by a bounds check.
+//           (global patch reads) and band (whole image in LDS; weights in
+//           LDS for conv1, in registers for the 64-output layers).
+// Dgrad:    dX from the dense, pre-masked dY via uniform taps (stride-2
+//           convs split into parity classes so every row in a tile has the
+//           same taps; no divergence).  Dense: one launch per parity class,
+//           tap table passed in, out-of-range taps dropped by a bounds
+//           check on global gathers.  Band (what the engine runs): one
+//           launch per layer, the image's dY staged once in LDS inside a
+//           zero halo for all classes, weights in registers, dX stored
+//           through LDS; bit-equal to dense.
 // Wgrad:    dWt(COUT,K) += dY^T @ patch in 32-row tiles with f32 atomics;
 //           fused ReLU mask + bias grad; chunked (patch tiles copied from
 //           global memory) and band (whole image + its dY in LDS, fragments
@@ -604,10 +609,21 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
 // instead of one per patch overlap: conv1 557 MB u8 re-dequant -> 154 MB,
 // conv3 9x re-read -> 1x).  Fused bias + ReLU as in conv_fwd_kernel.
 // ---------------------------------------------------------------------------
-// BAND_COLS: output columns computed per launch — a 64-out conv runs as two
-// launches with co0 = 0/32, halving the LDS weight slab so 2-3 workgroups
-// fit per CU; G::COUT is the output row stride.
+// BAND_COLS: output columns of the LDS weight slab.  Only conv1 (32 outputs)
+// runs this kernel in the engine; the 64-output layers keep their weights in
+// registers (conv_fwd_band64_kernel below) and stage each image once.
 constexpr int BAND_COLS = 32;
+
+// Default grids of the per-image kernels, in workgroups: 512 = the 2 per CU
+// that LDS (conv1) or VGPRs (register-resident weights) allow, times 256
+// CUs, one resident round with no tail.  Measured at 5440 images, medians of
+// two rounds, us, for 256 / 512 / 768 / 1024 / 2048 workgroups:
+//   conv1 fwd (4 ch) 246-248 / 149 / 198 / 160-161 / 160-162
+//   conv2 fwd        123-124 / 77-78 / 107 / 88-92 / 96-97
+//   conv3 fwd        72 / 48 / 57 / 53-54 / 63
+//   conv3 dgrad      70 / 53 / 62-63 / 58 / 67-68
+//   conv2 dgrad      101 / 72-73 / 90-91 / 75 / 78-82
+constexpr int BAND_WGS = 512;
 
 template <class G>
 __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
@@ -760,6 +776,277 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
         }
     }
     tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
+}
+
+// ---------------------------------------------------------------------------
+// Register-resident B operand.  A 64-column layer's weights are 64-74 KB: as
+// an LDS slab they crowd out the images and are refilled by every workgroup.
+// Split over the waves instead, a wave's 32 columns of the whole K extent
+// are K/32 * 2 fragments = at most 144 VGPRs, loaded ONCE per workgroup and
+// never re-read; the k loop is fully unrolled around them.
+//   b[ks][j] = W[(col0 + 16*j + lane%16) * K + 32*ks + 8*(lane/16) .. +7]
+// ---------------------------------------------------------------------------
+template <int KSTEPS>
+__device__ __forceinline__ void load_b_regs(bf16x8 (&b)[KSTEPS][2],
+                                            const __hip_bfloat16* W, int col0,
+                                            int lane) {
+    const __hip_bfloat16* p =
+        W + (long)(col0 + (lane & 15)) * (KSTEPS * 32) + (lane >> 4) * 8;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            b[ks][j] = load_bf16x8(p + (long)j * 16 * (KSTEPS * 32) + ks * 32);
+}
+
+// ---------------------------------------------------------------------------
+// conv_fwd_band for the 64-output layers: ONE launch, each image staged once
+// for both column halves.  Waves are 2 (row halves of the image's output
+// pixels) x 2 (32-column halves); the weights live in registers
+// (load_b_regs), so LDS holds only the image, in the GatherImage layout whose
+// output-pixel stride of 160 B keeps the 16-byte patch reads of 16
+// consecutive pixels off each other's banks.  The k order per output element
+// is conv_fwd_band_kernel's, so the outputs are bit-equal to it.
+// ---------------------------------------------------------------------------
+template <class G>
+__global__ __launch_bounds__(256, 2) void conv_fwd_band64_kernel(
+    const void* __restrict__ in,            // (N, INH, INW, CIN)
+    const __hip_bfloat16* __restrict__ Wt,  // (COUT, K)
+    const float* __restrict__ bias,
+    __hip_bfloat16* __restrict__ out,       // (N*NPIX, COUT)
+    int N, int imgs_per_wg) {
+    using Img = GatherImage<G>;
+    constexpr int K = G::K, NPIX = G::NPIX, KSTEPS = K / 32;
+    constexpr int NI = ((NPIX + 15) / 16 + 1) / 2;  // row frags per wave
+    static_assert(G::COUT == 64 && !G::IN_U8 && G::CIN % 32 == 0);
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_img[Img::SIZE];
+
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int wr = wave >> 1, col0 = (wave & 1) * 32;
+    const int frow = lane & 15, kseg = (lane >> 4) * 8;
+
+    bf16x8 b[KSTEPS][2];
+    load_b_regs<KSTEPS>(b, Wt, col0, lane);
+    float bias_c[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bias_c[j] = bias[col0 + j * 16 + frow];
+
+    // patch origin of this lane's row in each fragment, clamped into the
+    // image: rows past the last pixel compute a copy that is never stored
+    int pbase[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        int pp = min((wr * NI + i) * 16 + frow, NPIX - 1);
+        pbase[i] = (pp / G::OW * Img::RS + pp % G::OW * Img::PS) * G::S + kseg;
+    }
+
+    const long n0 = (long)blockIdx.x * imgs_per_wg;
+    const long n1 = min((long)N, n0 + imgs_per_wg);
+    for (long n = n0; n < n1; ++n) {
+        __syncthreads();
+        stage_image<G, Img>(s_img, in, n);
+        __syncthreads();
+
+        f32x4 acc[NI][2] = {};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            // k = (ky, kx, c) of the step's first element: a compile-time
+            // offset; the lane's kseg (in pbase) stays inside its pixel
+            constexpr int CIN = G::CIN;
+            const int rem = ks * 32 % G::KWC;
+            const int off = ks * 32 / G::KWC * Img::RS + rem / CIN * Img::PS
+                            + rem % CIN;
+            bf16x8 a[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                a[i] = *reinterpret_cast<const bf16x8*>(
+                    &s_img[pbase[i] + off]);
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a[i], b[ks][j], acc[i][j], 0, 0, 0);
+        }
+        for_each_acc(acc, lane, [&](int r, int c, float v) {
+            int pp = wr * NI * 16 + r;
+            if (pp < NPIX) {
+                v += bias_c[c / 16];
+                out[(n * NPIX + pp) * G::COUT + col0 + c] =
+                    f2bf(fmaxf(v, 0.f));
+            }
+        });
+    }
+}
+
+// ---------------------------------------------------------------------------
+// conv_dgrad_band: per-image dgrad, one launch per layer.  Same sums as
+// conv_dgrad_dense_kernel — k runs tap-major, co-minor, 32 per MFMA step, in
+// the parity class's tap order, out-of-image taps issued as zero fragments —
+// so the result is bit-equal to it; what changes is where the operands come
+// from and how dX leaves:
+//   dY  the image's dense pre-masked gradient is staged ONCE in LDS inside a
+//       zero halo (TH-1 / TW-1 pixels per side), so the tap of class row
+//       (yy, xx) is the 16-byte LDS read at pixel (yy - jy, xx - jx) with a
+//       compile-time tap offset and no bounds check.  The staged grid is the
+//       same for every parity class: all S*S classes run on one staged dY.
+//       Pixel stride 160 B and the row strides below were enumerated on the
+//       host over the ds_read_b128 lane groups for every 16-row fragment of
+//       both layers, row wraps included: no bank is hit twice.
+//   W   in registers (load_b_regs).  conv3 (one class): waves are 2 row
+//       halves x 2 column halves of 32.  conv2 (four classes of 32 columns):
+//       wave w owns class w, 64 VGPRs of weights.
+//   dX  the accumulators are assembled as the image's bf16 dX in LDS (the
+//       four classes interleave into whole rows), then masked by the layer
+//       below's ReLU and stored with 16-byte coalesced accesses.
+// The next image's dY and this image's mask are loaded into registers before
+// the MFMA loop; two barriers per image.
+// ---------------------------------------------------------------------------
+template <class G>
+struct DgradBand {
+    static constexpr int S = G::S, NCLS = S * S;
+    static constexpr int TH = G::KH / S, TW = G::KW / S;   // taps per class
+    static constexpr int HY = TH - 1, HX = TW - 1;         // halo
+    static constexpr int SH = G::OH + 2 * HY, SW = G::OW + 2 * HX;
+    static constexpr int PS = G::COUT + 16;                // 160 B
+    static constexpr int RS = NCLS == 1 ? 976 : 928;       // see above
+    static constexpr int DY_SIZE = SH * RS;
+    static constexpr int PSX = G::CIN + 8;                 // dX pixel stride
+    static constexpr int DX_SIZE = G::INH * G::INW * PSX;
+    static constexpr int K = G::TAPS * G::COUT, KSTEPS = K / 32;
+    static constexpr int NROWS = G::CLS_H * G::CLS_W;      // rows per class
+    static constexpr int NFRAG = (NROWS + 15) / 16;
+    // one class: 2 x 2 waves; four classes: one wave each, all its rows
+    static constexpr int NI = NCLS == 1 ? (NFRAG + 1) / 2 : NFRAG;
+    static constexpr int DY_CHUNKS = G::NPIX * G::COUT / 8;
+    static constexpr int DX_CHUNKS = G::IMG / 8;
+    static constexpr int NDY = (DY_CHUNKS + 255) / 256;
+    static constexpr int NDX = (DX_CHUNKS + 255) / 256;
+    static_assert(G::COUT == 64 && RS >= SW * PS && RS % 8 == 0);
+    static_assert((NCLS == 1 && G::CIN == 64) || (NCLS == 4 && G::CIN == 32),
+                  "wave split: 2x2 over 64 columns, or one class per wave");
+    static_assert((DY_SIZE + DX_SIZE) * 2 <= 64 * 1024);
+};
+
+template <class G, bool OUT_MASK>
+__global__ __launch_bounds__(256, 2) void conv_dgrad_band_kernel(
+    const __hip_bfloat16* __restrict__ dY,   // (N, OH, OW, COUT)
+    const __hip_bfloat16* __restrict__ Wd,   // (NCLS, CIN, TAPS*COUT)
+    const __hip_bfloat16* __restrict__ actx, // (N, INH, INW, CIN) or null
+    __hip_bfloat16* __restrict__ dX,         // (N, INH, INW, CIN)
+    int N, int imgs_per_wg) {
+    using D = DgradBand<G>;
+    constexpr int COUT = G::COUT, CIN = G::CIN;
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_dy[D::DY_SIZE];
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_dx[D::DX_SIZE];
+
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int cls = D::NCLS == 1 ? 0 : wave;
+    const int frag0 = D::NCLS == 1 ? (wave >> 1) * D::NI : 0;
+    const int col0 = D::NCLS == 1 ? (wave & 1) * 32 : 0;
+    const int py = cls / G::S, px = cls % G::S;
+    const int frow = lane & 15, kseg = (lane >> 4) * 8;
+
+    bf16x8 b[D::KSTEPS][2];
+    load_b_regs<D::KSTEPS>(b, Wd + (long)cls * CIN * D::K, col0, lane);
+
+    // staged-dY offset of this lane's class row in each fragment, at tap
+    // (0, 0); rows past the class grid read its last row and are not stored
+    int abase[D::NI];
+#pragma unroll
+    for (int i = 0; i < D::NI; ++i) {
+        int q = min((frag0 + i) * 16 + frow, D::NROWS - 1);
+        abase[i] = (q / G::CLS_W + D::HY) * D::RS
+                   + (q % G::CLS_W + D::HX) * D::PS + kseg;
+    }
+    // where this thread's 16-byte chunks of dY land in the halo'd image
+    int dyoff[D::NDY];
+#pragma unroll
+    for (int c = 0; c < D::NDY; ++c) {
+        int e8 = min((int)threadIdx.x + c * 256, D::DY_CHUNKS - 1);
+        int pix = e8 / (COUT / 8);
+        dyoff[c] = (pix / G::OW + D::HY) * D::RS
+                   + (pix % G::OW + D::HX) * D::PS + e8 % (COUT / 8) * 8;
+    }
+    auto load_dy = [&](bf16x8 (&pre)[D::NDY], long n) {
+        const __hip_bfloat16* g = dY + n * (G::NPIX * COUT);
+#pragma unroll
+        for (int c = 0; c < D::NDY; ++c) {
+            int e8 = threadIdx.x + c * 256;
+            if (e8 < D::DY_CHUNKS) pre[c] = load_bf16x8(g + e8 * 8);
+        }
+    };
+
+    const long n0 = (long)blockIdx.x * imgs_per_wg;
+    const long n1 = min((long)N, n0 + imgs_per_wg);
+    if (n0 >= n1) return;
+    bf16x8 pre[D::NDY];
+    load_dy(pre, n0);
+    for (int e = threadIdx.x * 8; e < D::DY_SIZE; e += 256 * 8)
+        *reinterpret_cast<bf16x8*>(&s_dy[e]) = zero_bf16x8();
+    __syncthreads();    // halo zeroed before anyone stages into the image
+
+    for (long n = n0; n < n1; ++n) {
+#pragma unroll
+        for (int c = 0; c < D::NDY; ++c)
+            if ((int)threadIdx.x + c * 256 < D::DY_CHUNKS)
+                *reinterpret_cast<bf16x8*>(&s_dy[dyoff[c]]) = pre[c];
+        __syncthreads();    // dY staged; the previous image's dX is stored
+        if (n + 1 < n1) load_dy(pre, n + 1);
+        bf16x8 mask[D::NDX];
+        if (OUT_MASK) {
+#pragma unroll
+            for (int c = 0; c < D::NDX; ++c) {
+                int e8 = threadIdx.x + c * 256;
+                if (e8 < D::DX_CHUNKS)
+                    mask[c] = load_bf16x8(actx + n * G::IMG + e8 * 8);
+            }
+        }
+
+        f32x4 acc[D::NI][2] = {};
+#pragma unroll
+        for (int ks = 0; ks < D::KSTEPS; ++ks) {
+            constexpr int PER_TAP = COUT / 32;
+            const int t = ks / PER_TAP;
+            const int off = -((t / D::TW) * D::RS + (t % D::TW) * D::PS)
+                            + (ks % PER_TAP) * 32;
+            bf16x8 a[D::NI];
+#pragma unroll
+            for (int i = 0; i < D::NI; ++i)
+                a[i] = *reinterpret_cast<const bf16x8*>(&s_dy[abase[i] + off]);
+#pragma unroll
+            for (int i = 0; i < D::NI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a[i], b[ks][j], acc[i][j], 0, 0, 0);
+        }
+
+        for_each_acc(acc, lane, [&](int r, int c, float v) {
+            int q = frag0 * 16 + r;
+            if (q < D::NROWS) {
+                int y = py + q / G::CLS_W * G::S, x = px + q % G::CLS_W * G::S;
+                s_dx[(y * G::INW + x) * D::PSX + col0 + c] = f2bf(v);
+            }
+        });
+        __syncthreads();    // dX assembled; every read of s_dy is done
+
+        __hip_bfloat16* gx = dX + n * G::IMG;
+#pragma unroll
+        for (int c = 0; c < D::NDX; ++c) {
+            int e8 = threadIdx.x + c * 256;
+            if (e8 < D::DX_CHUNKS) {
+                bf16x8 v = *reinterpret_cast<const bf16x8*>(
+                    &s_dx[e8 / (CIN / 8) * D::PSX + e8 % (CIN / 8) * 8]);
+                if (OUT_MASK) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        v[e] = ((float)mask[c][e] > 0.f) ? v[e] : (__bf16)0.f;
+                }
+                *reinterpret_cast<bf16x8*>(gx + e8 * 8) = v;
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -940,32 +1227,116 @@ torch::Tensor conv_dgrad_dense(torch::Tensor dY, torch::Tensor Wd,
     return dX;
 }
 
-// per-image band forward.  N = number of images (B*T).
+// images per workgroup and grid for the per-image kernels: `wgs` workgroups
+// at the most, every one with the same run of images but the last
+static void band_grid(int64_t N, int64_t wgs, int& imgs, int& grid) {
+    imgs = cdiv(N, std::max<int64_t>(1, wgs));
+    grid = cdiv(N, imgs);
+}
+
+// per-image band forward.  N = number of images (B*T).  max_wgs > 0 caps the
+// grid (tests push several images through one workgroup with it).
 torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
-                            torch::Tensor bias, int64_t conv_id, int64_t N) {
+                            torch::Tensor bias, int64_t conv_id, int64_t N,
+                            int64_t max_wgs) {
     const char* who = "conv_fwd_band";
     torch::Tensor out;
+    TORCH_CHECK(N > 0 && max_wgs >= 0, who, ": N must be positive and max_wgs "
+                "non-negative");
     // whole-image staging loads 8 bytes per lane for both conv1 variants
     int cin1 = conv1_cin(conv_id, in, N, 8, 8, who);
     dispatch_layer(conv_id, cin1, who, [&](auto g) {
         using G = decltype(g);
         check_weights<G>(Wt, who);
         check_input<G>(in, N, who);
+        TORCH_CHECK(Wt.is_cuda() && Wt.dtype() == torch::kBFloat16
+                    && Wt.is_contiguous()
+                    && reinterpret_cast<uintptr_t>(Wt.data_ptr()) % 16 == 0
+                    && bias.is_cuda() && bias.dtype() == torch::kFloat32
+                    && bias.is_contiguous() && bias.numel() == G::COUT, who,
+                    ": weights must be contiguous, 16-byte aligned bf16 and "
+                    "bias ", G::COUT, " f32, both on the device");
         out = torch::empty({N * G::NPIX, G::COUT},
                            in.options().dtype(torch::kBFloat16));
-        int imgs = cdiv(N, 2048);
-        int grid = cdiv(N, imgs);
-        // a 64-out layer runs as two 32-col launches (LDS weight slab halved)
-        for (int co0 = 0; co0 < G::COUT; co0 += BAND_COLS)
+        int imgs, grid;
+        auto stream = at::cuda::getCurrentCUDAStream().stream();
+        auto wt = reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr());
+        auto op = reinterpret_cast<__hip_bfloat16*>(out.data_ptr());
+        if constexpr (G::COUT == 64) {
+            // one launch for both column halves, weights in registers
+            band_grid(N, max_wgs > 0 ? max_wgs : BAND_WGS, imgs, grid);
             hipLaunchKernelGGL(
-                (conv_fwd_band_kernel<G>), dim3(grid), dim3(256), 0,
-                at::cuda::getCurrentCUDAStream().stream(), in.data_ptr(),
-                reinterpret_cast<const __hip_bfloat16*>(Wt.data_ptr()),
-                bias.data_ptr<float>(),
-                reinterpret_cast<__hip_bfloat16*>(out.data_ptr()), (int)N,
-                imgs, co0);
+                (conv_fwd_band64_kernel<G>), dim3(grid), dim3(256), 0, stream,
+                in.data_ptr(), wt, bias.data_ptr<float>(), op, (int)N, imgs);
+        } else {
+            // one-channel conv1 (14 KB images, 5 KB slab) keeps its 2048:
+            // 62 us there and at 1024, 72-73 us at 512, 113 at 256
+            band_grid(N, max_wgs > 0 ? max_wgs : (G::CIN == 1 ? 2048 : BAND_WGS),
+                      imgs, grid);
+            for (int co0 = 0; co0 < G::COUT; co0 += BAND_COLS)
+                hipLaunchKernelGGL(
+                    (conv_fwd_band_kernel<G>), dim3(grid), dim3(256), 0,
+                    stream, in.data_ptr(), wt, bias.data_ptr<float>(), op,
+                    (int)N, imgs, co0);
+        }
     });
     return out;
+}
+
+// per-image band dgrad (see conv_dgrad_band_kernel).  dY is the dense,
+// pre-masked upstream gradient; Wd holds every parity class's (CIN,
+// TAPS*COUT) slab, class (py, px) at index py*S + px; actx (optional) fuses
+// the ReLU mask of the conv below into the dX store.  conv2 and conv3 only.
+torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
+                              torch::Tensor actx, int64_t conv_id, int64_t N,
+                              int64_t max_wgs) {
+    const char* who = "conv_dgrad_band";
+    torch::Tensor dX;
+    TORCH_CHECK(conv_id == 2 || conv_id == 3, who,
+                ": only conv2 and conv3 have a dgrad, got conv_id ", conv_id);
+    TORCH_CHECK(N > 0 && max_wgs >= 0, who, ": N must be positive and max_wgs "
+                "non-negative");
+    dispatch_layer(conv_id, 0, who, [&](auto g) {
+        using G = decltype(g);
+        if constexpr (!G::IN_U8) {
+            using D = DgradBand<G>;
+            bool has_m = actx.defined() && actx.numel() > 0;
+            TORCH_CHECK(dY.numel() == N * G::NPIX * G::COUT, who,
+                        ": dY must hold N*", G::NPIX * G::COUT, " elements");
+            TORCH_CHECK(Wd.dim() >= 2 && Wd.numel() == D::NCLS * G::CIN * D::K
+                        && Wd.size(-1) == D::K && Wd.size(-2) == G::CIN, who,
+                        ": Wd must be (", D::NCLS, ", ", G::CIN, ", ", D::K,
+                        "), got ", Wd.sizes());
+            if (has_m)
+                TORCH_CHECK(actx.numel() == N * G::IMG, who,
+                            ": the mask must hold N*", G::IMG, " elements");
+            for (const torch::Tensor* t : {&dY, &Wd, &actx})
+                TORCH_CHECK((t == &actx && !has_m)
+                            || (t->is_cuda() && t->dtype() == torch::kBFloat16
+                                && t->is_contiguous()
+                                && reinterpret_cast<uintptr_t>(t->data_ptr())
+                                       % 16 == 0), who,
+                            ": dY, Wd and the mask must be contiguous, 16-byte "
+                            "aligned bf16 device tensors");
+            dX = torch::empty({N, G::INH, G::INW, G::CIN}, dY.options());
+            int imgs, grid;
+            band_grid(N, max_wgs > 0 ? max_wgs : BAND_WGS, imgs, grid);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(
+                    kernel, dim3(grid), dim3(256), 0,
+                    at::cuda::getCurrentCUDAStream().stream(),
+                    reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+                    reinterpret_cast<const __hip_bfloat16*>(Wd.data_ptr()),
+                    has_m ? reinterpret_cast<const __hip_bfloat16*>(
+                                actx.data_ptr()) : nullptr,
+                    reinterpret_cast<__hip_bfloat16*>(dX.data_ptr()), (int)N,
+                    imgs);
+            };
+            if (has_m) launch(conv_dgrad_band_kernel<G, true>);
+            else launch(conv_dgrad_band_kernel<G, false>);
+        }
+    });
+    return dX;
 }
 
 // per-image band wgrad (see conv_wgrad_band_kernel).  N = number of images.
