@@ -167,6 +167,16 @@ PRESETS = {
         action_dim=9, encoder="nature", gpu_replay=True, num_actors=256,
         buffer_capacity=4_000_000, vector_actors=True, actor_device="cuda",
     ),
+    # `mspacman` at batch sizes above the persistent LSTM's 64-row pass: the
+    # HIP engine runs them through the multi-pass LSTM launch (limit 256)
+    "mspacman_b128": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=False, batch_size=128,
+    ),
+    "mspacman_b256": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=False, batch_size=256,
+    ),
 }
 
 

@@ -261,6 +261,20 @@ class _NetPack:
             self.w2d = torch.stack(slabs).bfloat16().contiguous()  # (4,32,256)
 
 
+# batch rows of the persistent LSTM: one pass up to LSTM_SINGLE_ROWS
+# (lstm_fwd / lstm_bwd), the multi-pass launch up to MAX_BATCH_SIZE
+LSTM_SINGLE_ROWS = 64
+MAX_BATCH_SIZE = 256
+
+
+def check_batch_size(B, what="batch_size"):
+    """The HIP engine trains on at most MAX_BATCH_SIZE sequences per step."""
+    if not 1 <= int(B) <= MAX_BATCH_SIZE:
+        raise ValueError(
+            f"the HIP engine supports 1 <= batch_size <= {MAX_BATCH_SIZE} "
+            f"(the persistent LSTM's multi-pass limit); {what} = {int(B)}")
+
+
 class HipNetworkEngine:
     def __init__(self, online_net, target_net, device, config=None):
         c = config or cfg.get()
@@ -268,6 +282,7 @@ class HipNetworkEngine:
         assert c.encoder in ("nature", "impala") and c.hidden_dim == 512, \
             "HIP engine supports the nature/impala 512-hidden configs"
         assert tuple(c.obs_shape[1:]) == (84, 84)
+        check_batch_size(c.batch_size, "config.batch_size")
         self.C = c.obs_shape[0]
         self.impala = c.encoder == "impala"
         assert self.C in conv1_channels(c.encoder), \
@@ -529,6 +544,7 @@ class HipNetworkEngine:
         to overlap the RCCL all-reduce with the rest of the manual
         backward (graphs are bypassed in that case so the collectives can
         interleave)."""
+        check_batch_size(batch.obs.shape[0], "the batch's B")
         if bool(self._poison_pin.any()):
             raise RuntimeError(
                 "persistent LSTM kernel poisoned on a previous step "
@@ -593,7 +609,10 @@ class HipNetworkEngine:
         self._mark("lstm_input")
         Xo = X_o.view(B, T, 4 * H)
         Xt = X_t.view(B, T, 4 * H)
-        Ho, Co, Ht, Ct, stash = m.lstm_fwd(
+        # above 64 rows: the multi-pass launch (W_hh stays in LDS across
+        # passes of 64 or 128 rows); up to 64 the single-pass kernels
+        lstm_fwd = m.lstm_fwd_multi if B > LSTM_SINGLE_ROWS else m.lstm_fwd
+        Ho, Co, Ht, Ct, stash = lstm_fwd(
             Xo, Xt, self.online.whh_t, self.target.whh_t,
             init, init, lens, self.bar, True)
         self._poison_pin[0:1].copy_(self.bar[256:257], non_blocking=True)
@@ -659,8 +678,9 @@ class HipNetworkEngine:
         dHext = m.scatter_dh(dh_a, dh_v, row_of, B * T).view(B, T, H)
         self._mark("head_bwd")
 
-        dgates = m.lstm_bwd(stash, Co, Ho, dHext.contiguous(), ON.whh_bwd,
-                            lens, self.bar)
+        lstm_bwd = m.lstm_bwd_multi if B > LSTM_SINGLE_ROWS else m.lstm_bwd
+        dgates = lstm_bwd(stash, Co, Ho, dHext.contiguous(), ON.whh_bwd,
+                          lens, self.bar)
         self._poison_pin[1:2].copy_(self.bar[256:257], non_blocking=True)
         self._mark("lstm_bwd")
         dgates_flat = dgates.view(B * T, 4 * H)

@@ -94,6 +94,14 @@ torch::Tensor lstm_bwd(torch::Tensor stash, torch::Tensor Cout,
                        torch::Tensor Hout, torch::Tensor dHext,
                        torch::Tensor Whh_bwd, torch::Tensor lens,
                        torch::Tensor barrier_ws);
+std::vector<torch::Tensor> lstm_fwd_multi(
+    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
+    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
+    torch::Tensor barrier_ws, bool want_stash, int64_t rows);
+torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
+                             torch::Tensor Hout, torch::Tensor dHext,
+                             torch::Tensor Whh_bwd, torch::Tensor lens,
+                             torch::Tensor barrier_ws, int64_t rows);
 
 // impala_kernels.hip
 void conv3p_pool(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
@@ -183,6 +191,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("lstm_fwd", &lstm_fwd,
           "Persistent fused LSTM forward (dual-network, length-masked)");
     m.def("lstm_bwd", &lstm_bwd, "Persistent fused LSTM BPTT backward");
+    m.def("lstm_fwd_multi", &lstm_fwd_multi,
+          "Persistent fused LSTM forward for 1 <= B <= 256: one launch, "
+          "passes of `rows` (64 or 128; 0 = R2D2_LSTM_MULTI_ROWS / default) "
+          "batch rows with W_hh LDS-resident across passes",
+          py::arg("X0"), py::arg("X1"), py::arg("Whh0"), py::arg("Whh1"),
+          py::arg("init0"), py::arg("init1"), py::arg("lens"),
+          py::arg("barrier_ws"), py::arg("want_stash"), py::arg("rows") = 0);
+    m.def("lstm_bwd_multi", &lstm_bwd_multi,
+          "Persistent fused LSTM BPTT backward for 1 <= B <= 256 (multi-pass)",
+          py::arg("stash"), py::arg("Cout"), py::arg("Hout"),
+          py::arg("dHext"), py::arg("Whh_bwd"), py::arg("lens"),
+          py::arg("barrier_ws"), py::arg("rows") = 0);
     m.def("assemble_rin", &assemble_rin,
           "fused LSTM-input row assembly (latent | action | reward | pad)");
     m.def("barrier_bench", &barrier_bench, "grid barrier microbench");

@@ -605,6 +605,411 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Multi-pass kernels: batches above 64 rows in ONE launch.
+//
+// The batch is cut into passes of P rows (P = 64 or 128).  A workgroup owns
+// one (net, 16-unit slice, row group) of a pass and, after the T steps of
+// pass p, moves on to pass p+1 with its W_hh slice still in LDS — a host
+// loop of 64-row launches would reload all 128 x 66 KB of weights and run
+// a workspace reset per chunk.  Only the per-pass state is re-initialised
+// (s_c / Hout[:,0] forward, s_dh / s_dc backward).  Every pass, a partial
+// last one included, runs the layout a 64-row launch uses today (forward
+// BROWS=32, backward BROWS=16 / KSPLIT=4) with the same per-element
+// accumulation order, so every full 64-row chunk is bit-equal to lstm_fwd /
+// lstm_bwd on those rows.
+//
+// Handoff invariant.  The counters are zeroed once per launch and only ever
+// grow.  Each workgroup publishes T+1 times per pass (once after the pass
+// init, once per step), so when it awaits step t of pass p it has itself
+// published  n = p*(T+1) + t + 1  times (backward: p*(T+1) + T - t), and
+// the await target is WGS * n.  No workgroup of the group can publish more
+// than n times without first passing this same await (the pass-init
+// publish follows the last step's publish without an await in between, but
+// the NEXT await is again at the publisher's own count).  So while any
+// workgroup is still waiting for n, every count is <= n, and the sum
+// reaches WGS * n only when ALL counts equal n — the sum threshold stays
+// equivalent to per-producer flags across pass boundaries.  The pass-init
+// publish releases only rows of the new pass (Hout[:, 0]), which nobody
+// reads before passing an await of that pass.
+//
+// Row groups past the end of the batch (Bl <= 0) write nothing but still
+// await and publish, like the empty quarters of a small batch.
+// ---------------------------------------------------------------------------
+template <int H, int BROWS, int UNITS>
+__global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
+    const __hip_bfloat16* __restrict__ X0,    // (B, T, 4H)
+    const __hip_bfloat16* __restrict__ X1,    // or null
+    const __hip_bfloat16* __restrict__ Whh0,  // (4H, H) row-major
+    const __hip_bfloat16* __restrict__ Whh1,
+    const float* __restrict__ init0,          // (2, B, H): h0, c0
+    const float* __restrict__ init1,
+    const int* __restrict__ lens,             // (B,)
+    __hip_bfloat16* __restrict__ Hout0,       // (B, T+1, H)
+    __hip_bfloat16* __restrict__ Hout1,
+    float* __restrict__ Cout0,                // (B, T+1, H)
+    float* __restrict__ Cout1,
+    __hip_bfloat16* __restrict__ stash0,      // (B, T, 4H) post-nonlin gates
+    GridBar* bar, int B, int T, int ngroups, int npasses) {
+    constexpr int WGS = H / UNITS;            // producers per counter group
+    constexpr int GCOLS = 4 * UNITS;
+    static_assert(GCOLS == 64, "wave tiling below is the 4-col-wave layout");
+    const int wgs_per_net = WGS * ngroups;
+    const int net = blockIdx.x / wgs_per_net;
+    const int rem = blockIdx.x % wgs_per_net;
+    const int grp = rem / WGS;
+    const int wid = rem % WGS;
+    const int u0 = wid * UNITS;
+    const int P = ngroups * BROWS;            // rows per pass
+
+    const __hip_bfloat16* X = net ? X1 : X0;
+    const __hip_bfloat16* Whh = net ? Whh1 : Whh0;
+    const float* init = net ? init1 : init0;
+    __hip_bfloat16* Hout = net ? Hout1 : Hout0;
+    float* Cout = net ? Cout1 : Cout0;
+    __hip_bfloat16* stash = net ? nullptr : stash0;
+    unsigned* ctr = &bar->flags[(net * ngroups + grp) * 32];
+
+    __shared__ __hip_bfloat16 s_whh[GCOLS][H + 8];
+    __shared__ __hip_bfloat16 s_h[BROWS][H + 8];
+    __shared__ float s_gates[BROWS][GCOLS + 4];
+    __shared__ float s_c[BROWS][UNITS];
+    __shared__ __hip_bfloat16 s_hrow[BROWS][UNITS];
+
+    // loaded ONCE for all passes
+    for (int e = threadIdx.x * 8; e < GCOLS * H; e += blockDim.x * 8) {
+        int c = e / H;
+        int k = e % H;
+        int g = c / UNITS, j = c % UNITS;
+        lstore8(&s_whh[c][k],
+                load_bf16x8(Whh + (long)(g * H + u0 + j) * H + k));
+    }
+
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x & (WAVE - 1);
+    constexpr int NFRAG = BROWS / 16;
+    const int wcol0 = wave * 16;
+    const int frow = lane & 15;
+    const int kseg = (lane >> 4) * 8;
+    constexpr int CHUNKS = (BROWS * H) / 8;
+
+    for (int pass = 0; pass < npasses; ++pass) {
+        const int b0 = pass * P + grp * BROWS;
+        const int Bl = min(B - b0, BROWS);    // <= 0: empty row group
+        const unsigned base_pub = (unsigned)pass * (unsigned)(T + 1);
+        // h0 -> Hout[:,0] (this wg's slice); c0 -> LDS-resident cell state
+        for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
+            int bl = p / UNITS, j = p % UNITS;
+            int b = b0 + bl;
+            int u = u0 + j;
+            Hout[((long)b * (T + 1)) * H + u] = f2bf(init[(long)b * H + u]);
+            Cout[((long)b * (T + 1)) * H + u] = init[((long)B + b) * H + u];
+            s_c[bl][j] = init[((long)B + b) * H + u];
+        }
+        publish_count(ctr);
+
+        for (int t = 0; t < T; ++t) {
+            if (!await_count(ctr, (unsigned)WGS * (base_pub + t + 1),
+                             &bar->poison))
+                return;
+            // bulk-stage this group's h_prev (Bl x H) into LDS
+            {
+                const long base = (long)t * H;
+#pragma unroll
+                for (int e = threadIdx.x; e < CHUNKS; e += 256) {
+                    int row = e / (H / 8);
+                    int k8 = (e % (H / 8)) * 8;
+                    bf16x8 v = (row < Bl)
+                        ? load_bf16x8(Hout + ((long)(b0 + row) * (T + 1))
+                                      * H + base + k8)
+                        : zero_bf16x8();
+                    lstore8(&s_h[row][k8], v);
+                }
+            }
+            __syncthreads();
+
+            // gates = h_prev @ Whh_slice^T  (all-LDS MFMA)
+            f32x4 acc[NFRAG] = {};
+#pragma unroll
+            for (int k0 = 0; k0 < H; k0 += 32) {
+                bf16x8 bfr = load_bf16x8(&s_whh[wcol0 + frow][k0 + kseg]);
+#pragma unroll
+                for (int i = 0; i < NFRAG; ++i) {
+                    bf16x8 afr =
+                        load_bf16x8(&s_h[i * 16 + frow][k0 + kseg]);
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        afr, bfr, acc[i], 0, 0, 0);
+                }
+            }
+            {
+                int ccol = lane & 15;
+                int crow = (lane >> 4) * 4;
+#pragma unroll
+                for (int i = 0; i < NFRAG; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        s_gates[i * 16 + crow + r][wcol0 + ccol] = acc[i][r];
+            }
+            __syncthreads();
+            // + X[t] (vectorized), then nonlinearities + state advance
+            {
+                int row = threadIdx.x / 4;
+                int g = threadIdx.x % 4;
+                if (row < Bl) {
+#pragma unroll
+                    for (int j8 = 0; j8 < UNITS; j8 += 8) {
+                        bf16x8 x8 = load_bf16x8(
+                            X + ((long)(b0 + row) * T + t) * 4 * H + g * H
+                            + u0 + j8);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            s_gates[row][g * UNITS + j8 + j] += (float)x8[j];
+                    }
+                }
+            }
+            __syncthreads();
+            for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
+                int b = p / UNITS, j = p % UNITS;
+                bool active = t < lens[b0 + b];
+                float i_ = 0.f, f_ = 0.f, g_ = 0.f, o_ = 0.f;
+                float c = s_c[b][j], h;
+                if (active) {
+                    i_ = sigmoidf_(s_gates[b][0 * UNITS + j]);
+                    f_ = sigmoidf_(s_gates[b][1 * UNITS + j]);
+                    g_ = tanhf(s_gates[b][2 * UNITS + j]);
+                    o_ = sigmoidf_(s_gates[b][3 * UNITS + j]);
+                    c = f_ * c + i_ * g_;
+                    h = o_ * tanhf(c);
+                } else {
+                    h = (float)*(const __bf16*)&s_h[b][u0 + j];
+                }
+                s_c[b][j] = c;
+                *(__bf16*)&s_hrow[b][j] = (__bf16)h;
+                s_gates[b][0 * UNITS + j] = i_;
+                s_gates[b][1 * UNITS + j] = f_;
+                s_gates[b][2 * UNITS + j] = g_;
+                s_gates[b][3 * UNITS + j] = o_;
+            }
+            __syncthreads();
+            // vectorized writers: h slice, c, gate stash
+            {
+                int tid = threadIdx.x;
+                constexpr int H8 = UNITS / 8;    // 16-B pieces per h row
+                if (tid < 64 * H8) {
+                    int b = tid / H8, piece = tid % H8;
+                    if (b < Bl) {
+                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H
+                                   + u0 + piece * 8;
+                        lstore8(Hout + off, *reinterpret_cast<bf16x8*>(
+                            &s_hrow[b][piece * 8]));
+                    }
+                } else {
+                    int t2 = tid - 128;
+                    constexpr int C4 = UNITS / 4;  // float4 pieces per c row
+                    static_assert(BROWS * C4 <= 128, "c-writer thread budget");
+                    static_assert(64 * H8 == 128, "h writers fill [0, 128)");
+                    int b = t2 / C4, ch = t2 % C4;
+                    if (b < Bl) {
+                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H
+                                   + u0 + ch * 4;
+                        *reinterpret_cast<float4*>(Cout + off) =
+                            *reinterpret_cast<float4*>(&s_c[b][ch * 4]);
+                    }
+                }
+            }
+            if (stash) {
+                int row = threadIdx.x / 4;
+                int g = threadIdx.x % 4;
+                if (row < Bl) {
+#pragma unroll
+                    for (int j8 = 0; j8 < UNITS; j8 += 8) {
+                        bf16x8 v;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            v[j] = (__bf16)s_gates[row][g * UNITS + j8 + j];
+                        lstore8(stash + ((long)(b0 + row) * T + t) * 4 * H
+                                + g * H + u0 + j8, v);
+                    }
+                }
+            }
+            publish_count(ctr);
+        }
+    }
+}
+
+template <int H, int BROWS, int UNITS>
+__global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
+    const __hip_bfloat16* __restrict__ stash,  // (B, T, 4H) i,f,g,o
+    const float* __restrict__ Cout,            // (B, T+1, H)
+    const float* __restrict__ dHext,           // (B, T, H) upstream
+    const __hip_bfloat16* __restrict__ Whh_bwd,// (H, 4H): W_hh^T row-major
+    const int* __restrict__ lens,
+    __hip_bfloat16* __restrict__ dgates,       // (B, T, 4H) out
+    GridBar* bar, int B, int T, int ngroups, int npasses) {
+    static_assert(BROWS == 16 && UNITS == 16, "the KSPLIT=4 quarter layout");
+    constexpr int WGS = H / UNITS;
+    constexpr int KSPLIT = 4;
+    const int grp = blockIdx.x / WGS;
+    const int wid = blockIdx.x % WGS;
+    const int u0 = wid * UNITS;
+    const int P = ngroups * BROWS;             // rows per pass
+
+    __shared__ __hip_bfloat16 s_wb[UNITS][4 * H + 8];
+    __shared__ float s_dh[BROWS][UNITS + 1];
+    __shared__ float s_dc[BROWS][UNITS + 1];
+    __shared__ float s_rec[KSPLIT][BROWS][UNITS + 1];
+    __shared__ __hip_bfloat16 s_dgout[BROWS][4 * UNITS + 8];
+
+    unsigned* ctr = &bar->flags[grp * 32];
+
+    // loaded ONCE for all passes
+    for (int e = threadIdx.x * 8; e < UNITS * 4 * H; e += blockDim.x * 8) {
+        int c = e / (4 * H);
+        int k = e % (4 * H);
+        lstore8(&s_wb[c][k], load_bf16x8(Whh_bwd + (long)(u0 + c) * 4 * H + k));
+    }
+
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wk = wave;                       // this wave's quarter of 4H
+    const int frow = lane & 15;
+    const int kseg = (lane >> 4) * 8;
+    constexpr int NCHUNK = 4 * H / 32;
+    const int c0 = wk * (NCHUNK / KSPLIT);
+    const int cN = c0 + NCHUNK / KSPLIT;
+
+    for (int pass = 0; pass < npasses; ++pass) {
+        const int b0 = pass * P + grp * BROWS;
+        const int Bl = min(B - b0, BROWS);     // <= 0: empty row group
+        const unsigned base_pub = (unsigned)pass * (unsigned)(T + 1);
+        for (int p = threadIdx.x; p < BROWS * UNITS; p += blockDim.x) {
+            s_dh[p / UNITS][p % UNITS] = 0.f;
+            s_dc[p / UNITS][p % UNITS] = 0.f;
+        }
+        publish_count(ctr);
+
+        for (int t = T - 1; t >= 0; --t) {
+            unsigned need = (unsigned)(T - t);  // pieces published for t+1
+            if (!await_count(ctr, (unsigned)WGS * (base_pub + need),
+                             &bar->poison))
+                return;
+            // rec(B,UNITS) = dgates_{t+1}(B,4H) @ s_wb^T, 4-deep register
+            // prefetch ring on the dgates stream
+            if (t < T - 1) {
+                const int arow_l = frow;
+                const __hip_bfloat16* dgrow =
+                    dgates + ((long)(b0 + arow_l) * T + t + 1) * 4 * H;
+                const bool rvalid = arow_l < Bl;
+                f32x4 acc = {};
+                bf16x8 a0 = rvalid ? load_bf16x8(dgrow + (c0 + 0) * 32 + kseg)
+                    : zero_bf16x8();
+                bf16x8 a1 = rvalid ? load_bf16x8(dgrow + (c0 + 1) * 32 + kseg)
+                    : zero_bf16x8();
+                bf16x8 a2 = rvalid ? load_bf16x8(dgrow + (c0 + 2) * 32 + kseg)
+                    : zero_bf16x8();
+                bf16x8 a3 = rvalid ? load_bf16x8(dgrow + (c0 + 3) * 32 + kseg)
+                    : zero_bf16x8();
+#pragma unroll 4
+                for (int kc = c0; kc < cN; kc += 4) {
+                    bf16x8 w0 = load_bf16x8(&s_wb[frow][(kc + 0) * 32 + kseg]);
+                    bf16x8 w1 = load_bf16x8(&s_wb[frow][(kc + 1) * 32 + kseg]);
+                    bf16x8 w2 = load_bf16x8(&s_wb[frow][(kc + 2) * 32 + kseg]);
+                    bf16x8 w3 = load_bf16x8(&s_wb[frow][(kc + 3) * 32 + kseg]);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, acc, 0, 0, 0);
+                    if (kc + 4 < cN)
+                        a0 = rvalid ? load_bf16x8(dgrow + (kc + 4) * 32 + kseg)
+                            : zero_bf16x8();
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, acc, 0, 0, 0);
+                    if (kc + 5 < cN)
+                        a1 = rvalid ? load_bf16x8(dgrow + (kc + 5) * 32 + kseg)
+                            : zero_bf16x8();
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w2, acc, 0, 0, 0);
+                    if (kc + 6 < cN)
+                        a2 = rvalid ? load_bf16x8(dgrow + (kc + 6) * 32 + kseg)
+                            : zero_bf16x8();
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, w3, acc, 0, 0, 0);
+                    if (kc + 7 < cN)
+                        a3 = rvalid ? load_bf16x8(dgrow + (kc + 7) * 32 + kseg)
+                            : zero_bf16x8();
+                }
+                int ccol = lane & 15;
+                int crow = (lane >> 4) * 4;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    s_rec[wk][crow + r][ccol] = acc[r];
+            }
+            __syncthreads();
+            for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
+                int b = p / UNITS, jl = p % UNITS;
+                int bg = b0 + b;
+                int u = u0 + jl;
+                float dh, dc_in;
+                bool last = (t == T - 1);
+                bool active_next = !last && ((t + 1) < lens[bg]);
+                float ext = dHext[((long)bg * T + t) * H + u];
+                float rec = s_rec[0][b][jl];
+#pragma unroll
+                for (int kk = 1; kk < KSPLIT; ++kk) rec += s_rec[kk][b][jl];
+                if (last) {
+                    dh = ext;
+                    dc_in = 0.f;
+                } else if (active_next) {
+                    long so1 = ((long)bg * T + t + 1) * 4 * H + u;
+                    float f_next = bf2f(stash[so1 + H]);
+                    dh = ext + rec;
+                    dc_in = s_dc[b][jl] * f_next;
+                } else {
+                    dh = ext + s_dh[b][jl];
+                    dc_in = s_dc[b][jl];
+                }
+                bool active = t < lens[bg];
+                long so = ((long)bg * T + t) * 4 * H + u;
+                float di = 0.f, df = 0.f, dg = 0.f, do_ = 0.f;
+                if (active) {
+                    float i_ = bf2f(stash[so]);
+                    float f_ = bf2f(stash[so + H]);
+                    float g_ = bf2f(stash[so + 2 * H]);
+                    float o_ = bf2f(stash[so + 3 * H]);
+                    float tc = tanhf(Cout[((long)bg * (T + 1) + t + 1) * H + u]);
+                    float c_prev = Cout[((long)bg * (T + 1) + t) * H + u];
+                    float dc = dc_in + dh * o_ * (1.f - tc * tc);
+                    di = dc * g_ * i_ * (1.f - i_);
+                    df = dc * c_prev * f_ * (1.f - f_);
+                    dg = dc * i_ * (1.f - g_ * g_);
+                    do_ = dh * tc * o_ * (1.f - o_);
+                    s_dh[b][jl] = dh;
+                    s_dc[b][jl] = dc;
+                } else {
+                    s_dh[b][jl] = dh;
+                    s_dc[b][jl] = dc_in;
+                }
+                *(__bf16*)&s_dgout[b][0 * UNITS + jl] = (__bf16)di;
+                *(__bf16*)&s_dgout[b][1 * UNITS + jl] = (__bf16)df;
+                *(__bf16*)&s_dgout[b][2 * UNITS + jl] = (__bf16)dg;
+                *(__bf16*)&s_dgout[b][3 * UNITS + jl] = (__bf16)do_;
+            }
+            __syncthreads();
+            // vectorized dgates writes: thread (b, g) -> UNITS/8 x 16 B
+            {
+                int tid = threadIdx.x;
+                int b = tid / 4;
+                int g = tid % 4;
+                if (b < Bl) {
+#pragma unroll
+                    for (int rep = 0; rep < UNITS / 8; ++rep) {
+                        long off = ((long)(b0 + b) * T + t) * 4 * H + g * H
+                                   + u0 + rep * 8;
+                        lstore8(dgates + off,
+                                *reinterpret_cast<bf16x8*>(
+                                    &s_dgout[b][g * UNITS + rep * 8]));
+                    }
+                }
+            }
+            publish_count(ctr);
+        }
+    }
+}
+
 // counter-aggregated handoff microbench: ONE atomic counter per group —
 // publish = single atomicAdd, await = poll one word until nblocks*(t+1).
 __global__ void handoff_counter_bench_kernel(GridBar* bar, int steps,
@@ -922,5 +1327,132 @@ torch::Tensor lstm_bwd(torch::Tensor stash, torch::Tensor Cout,
         LSTMB(64, 16);
     }
 #undef LSTMB
+    return dgates;
+}
+
+// ---------------------------------------------------------------------------
+// Multi-pass entry points (1 <= B <= 256).  `rows` is the pass size P: 64
+// (128 workgroups, today's grid) or 128 (256 workgroups); 0 takes
+// R2D2_LSTM_MULTI_ROWS, default LSTM_MULTI_ROWS_DEFAULT.
+// ---------------------------------------------------------------------------
+#define LSTM_MULTI_MAX_B 256
+#define LSTM_MULTI_ROWS_DEFAULT 128
+
+static int lstm_multi_rows(int64_t rows) {
+    static const int rows_env = [] {
+        const char* e = getenv("R2D2_LSTM_MULTI_ROWS");
+        int v = e ? atoi(e) : LSTM_MULTI_ROWS_DEFAULT;
+        return (v == 64 || v == 128) ? v : LSTM_MULTI_ROWS_DEFAULT;
+    }();
+    TORCH_CHECK(rows == 0 || rows == 64 || rows == 128,
+                "rows per pass must be 64 or 128 (0 = default), got ", rows);
+    return rows ? (int)rows : rows_env;
+}
+
+static void lstm_check_ws(const torch::Tensor& ws) {
+    TORCH_CHECK(ws.defined() && ws.is_cuda() && ws.is_contiguous()
+                && ws.scalar_type() == torch::kInt32
+                && ws.numel() * 4 >= (long)sizeof(GridBar),
+                "barrier_ws must be a contiguous CUDA int32 tensor of >= ",
+                sizeof(GridBar) / 4, " words");
+}
+
+std::vector<torch::Tensor> lstm_fwd_multi(
+    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
+    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
+    torch::Tensor barrier_ws, bool want_stash, int64_t rows) {
+    TORCH_CHECK(X0.defined() && X0.dim() == 3, "X0 must be (B, T, 4H)");
+    long B = X0.size(0), T = X0.size(1);
+    long H4 = X0.size(2);
+    long H = H4 / 4;
+    TORCH_CHECK(H4 == 2048, "lstm_fwd_multi is instantiated for H=512");
+    TORCH_CHECK(B >= 1 && B <= LSTM_MULTI_MAX_B,
+                "1 <= B <= 256 per multi-pass launch, got B = ", B);
+    const int P = lstm_multi_rows(rows);
+    bool two = X1.defined() && X1.numel() > 0;
+    lstm_check(X0, "X0", torch::kBFloat16, {B, T, H4});
+    lstm_check(Whh0, "Whh0", torch::kBFloat16, {H4, H});
+    lstm_check(init0, "init0", torch::kFloat32, {2, B, H});
+    lstm_check(lens, "lens", torch::kInt32, {B});
+    if (two) {
+        lstm_check(X1, "X1", torch::kBFloat16, {B, T, H4});
+        lstm_check(Whh1, "Whh1", torch::kBFloat16, {H4, H});
+        lstm_check(init1, "init1", torch::kFloat32, {2, B, H});
+    }
+    lstm_check_ws(barrier_ws);
+
+    auto bf = X0.options();
+    auto f32 = X0.options().dtype(torch::kFloat32);
+    auto H0 = torch::empty({B, T + 1, H}, bf);
+    auto C0 = torch::empty({B, T + 1, H}, f32);
+    auto H1 = two ? torch::empty({B, T + 1, H}, bf) : torch::Tensor();
+    auto C1 = two ? torch::empty({B, T + 1, H}, f32) : torch::Tensor();
+    auto stash = want_stash ? torch::empty({B, T, H4}, bf) : torch::Tensor();
+
+    const int ngroups = P / 32;                 // 32-row groups per pass
+    const int npasses = (int)((B + P - 1) / P);
+    const int nblocks = (int)(H / 16) * ngroups * (two ? 2 : 1);
+    static_assert(2 * (128 / 32) * 32 <= LSTM_MAX_FLAGS, "counter groups");
+    auto stream = at::cuda::getCurrentCUDAStream();
+    zero_ws(barrier_ws, stream.stream());
+    auto bp = [](torch::Tensor& t) {
+        return t.defined()
+            ? reinterpret_cast<__hip_bfloat16*>(t.data_ptr()) : nullptr;
+    };
+    hipLaunchKernelGGL((lstm_fwd_multi_kernel<512, 32, 16>), dim3(nblocks),
+        dim3(256), 0, stream.stream(),
+        reinterpret_cast<const __hip_bfloat16*>(X0.data_ptr()),
+        two ? reinterpret_cast<const __hip_bfloat16*>(X1.data_ptr()) : nullptr,
+        reinterpret_cast<const __hip_bfloat16*>(Whh0.data_ptr()),
+        two ? reinterpret_cast<const __hip_bfloat16*>(Whh1.data_ptr()) : nullptr,
+        init0.data_ptr<float>(),
+        two ? init1.data_ptr<float>() : nullptr,
+        lens.data_ptr<int>(), bp(H0), bp(H1),
+        C0.data_ptr<float>(), two ? C1.data_ptr<float>() : nullptr,
+        want_stash ? bp(stash) : nullptr,
+        reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),
+        (int)B, (int)T, ngroups, npasses);
+
+    std::vector<torch::Tensor> out = {H0, C0};
+    out.push_back(two ? H1 : torch::Tensor());
+    out.push_back(two ? C1 : torch::Tensor());
+    out.push_back(want_stash ? stash : torch::Tensor());
+    return out;
+}
+
+torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
+                             torch::Tensor Hout, torch::Tensor dHext,
+                             torch::Tensor Whh_bwd, torch::Tensor lens,
+                             torch::Tensor barrier_ws, int64_t rows) {
+    TORCH_CHECK(stash.defined() && stash.dim() == 3,
+                "stash must be (B, T, 4H)");
+    long B = stash.size(0), T = stash.size(1), H4 = stash.size(2);
+    long H = H4 / 4;
+    TORCH_CHECK(H4 == 2048, "lstm_bwd_multi is instantiated for H=512");
+    TORCH_CHECK(B >= 1 && B <= LSTM_MULTI_MAX_B,
+                "1 <= B <= 256 per multi-pass launch, got B = ", B);
+    const int P = lstm_multi_rows(rows);
+    lstm_check(stash, "stash", torch::kBFloat16, {B, T, H4});
+    lstm_check(Cout, "Cout", torch::kFloat32, {B, T + 1, H});
+    lstm_check(Hout, "Hout", torch::kBFloat16, {B, T + 1, H});
+    lstm_check(dHext, "dHext", torch::kFloat32, {B, T, H});
+    lstm_check(Whh_bwd, "Whh_bwd", torch::kBFloat16, {H, H4});
+    lstm_check(lens, "lens", torch::kInt32, {B});
+    lstm_check_ws(barrier_ws);
+    auto dgates = torch::empty({B, T, H4}, stash.options());
+    const int ngroups = P / 16;                 // 16-row groups per pass
+    const int npasses = (int)((B + P - 1) / P);
+    const int nblocks = (int)(H / 16) * ngroups;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    zero_ws(barrier_ws, stream.stream());
+    hipLaunchKernelGGL((lstm_bwd_multi_kernel<512, 16, 16>), dim3(nblocks),
+        dim3(256), 0, stream.stream(),
+        reinterpret_cast<const __hip_bfloat16*>(stash.data_ptr()),
+        Cout.data_ptr<float>(), dHext.data_ptr<float>(),
+        reinterpret_cast<const __hip_bfloat16*>(Whh_bwd.data_ptr()),
+        lens.data_ptr<int>(),
+        reinterpret_cast<__hip_bfloat16*>(dgates.data_ptr()),
+        reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),
+        (int)B, (int)T, ngroups, npasses);
     return dgates;
 }

@@ -707,7 +707,9 @@ class Learner:
                 and len(c.obs_shape) == 3
                 and c.obs_shape[0] in conv1_channels(c.encoder)
                 and self.device.type == "cuda"):
-            from .ops.engine import HipNetworkEngine
+            from .ops.engine import HipNetworkEngine, check_batch_size
+            # fail here, not inside the extension at the first update
+            check_batch_size(c.batch_size, "config.batch_size")
             self.engine = HipNetworkEngine(self.online_net, self.target_net,
                                            self.device, c)
             # device-resident weight distribution to same-GPU VectorActors
