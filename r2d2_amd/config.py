@@ -74,6 +74,10 @@ class Config:
     dtype: str = "bf16"                          # compute dtype on GPU ('bf16'|'fp32')
     use_hip_kernels: bool = True                 # HIP path on GPU; eager is the CPU/golden path
     gpu_replay: bool = True                      # GPU-resident block store + sum-tree
+    # VectorActor ticks through HipInference.step (fused LSTM-cell and
+    # dueling-head kernels, three launches after the encoder) instead of
+    # HipInference.forward; only read where the K15 path is active
+    fused_actor_step: bool = False
     log_interval: int = 10                       # seconds; reference: config.py (log_interval)
     metrics_path: Optional[str] = None           # JSONL metrics emit (None = console only)
     # host-replay persistence (elastic resume; the reference never saves

@@ -833,3 +833,42 @@ class HipInference:
         val2 = m.gemm_bias_act(val1, p.wv2t, p.bv2, 0, True)
         q = m.dueling_combine(adv2, val2, self.A)
         return q, (h1.view(1, E, 512), c1.view(1, E, 512))
+
+    @torch.no_grad()
+    def step(self, obs_u8_nchw, last_action, last_reward, hidden):
+        """The fused tick: `forward`'s encoder calls, then three launches
+        (ops/hip/actor_step_kernels.hip) — LSTM cell, head hidden layers,
+        head outputs + dueling combine + greedy action — and no torch op in
+        between.  Same operands as `forward`.  Returns (q (E, A) f32,
+        greedy (E,) int32, (h', c')); greedy is the first index of the row
+        maximum of q.  h' and c' are fresh tensors, never the inputs'
+        storage."""
+        m = self.m
+        E = obs_u8_nchw.shape[0]
+        obs_hwc = obs_u8_nchw.permute(0, 2, 3, 1).contiguous()
+        if self.impala:
+            lat, _ = impala_ops.encoder_fwd(m, self.pack.imp, obs_hwc, False)
+        else:
+            p = self.pack
+            a1 = m.conv_fwd(obs_hwc, p.w1t, p.b1, 1, E, 84, 84, 20, 20, True)
+            a2 = m.conv_fwd(a1, p.w2t, p.b2, 2, E, 20, 20, 9, 9, True)
+            a3 = m.conv_fwd(a2, p.w3t, p.b3, 3, E, 9, 9, 7, 7, True)
+            lat = m.gemm_bias_act(a3.view(E, 3136), p.wft, p.bf, 1, False)
+        p = self.pack
+        h0, c0 = hidden
+        dev = lat.device
+        hc = torch.empty(2, E, 512, dtype=torch.float32, device=dev)
+        hid = torch.empty(3, E, 512, dtype=torch.bfloat16, device=dev)
+        q = torch.empty(E, self.A, dtype=torch.float32, device=dev)
+        greedy = torch.empty(E, dtype=torch.int32, device=dev)
+        # float()/contiguous() return their argument for the f32 contiguous
+        # tensors VectorActor holds
+        m.lstm_cell_step(lat.contiguous(), last_action.float().contiguous(),
+                         last_reward.reshape(E).float().contiguous(),
+                         h0.reshape(E, 512), c0.reshape(E, 512),
+                         p.wih_t, p.whh_t, p.lstm_bias, hc[0], hc[1], hid[0])
+        m.head_hidden_step(hid[0], p.wa1t, p.ba1, p.wv1t, p.bv1,
+                           hid[1], hid[2])
+        m.head_out_step(hid[1], hid[2], p.wa2t, p.ba2, p.wv2t, p.bv2,
+                        q, greedy)
+        return q, greedy, (hc[0:1], hc[1:2])

@@ -134,6 +134,20 @@ void adam_step(torch::Tensor param, torch::Tensor grad, torch::Tensor m,
                double lr, double beta1, double beta2, double eps,
                int64_t step);
 
+// actor_step_kernels.hip
+void lstm_cell_step(torch::Tensor latent, torch::Tensor last_action,
+                    torch::Tensor last_reward, torch::Tensor h0,
+                    torch::Tensor c0, torch::Tensor wih_t,
+                    torch::Tensor whh_t, torch::Tensor lstm_bias,
+                    torch::Tensor h1, torch::Tensor c1, torch::Tensor hb,
+                    int64_t units, int64_t rows);
+void head_hidden_step(torch::Tensor hb, torch::Tensor wa1t, torch::Tensor ba1,
+                      torch::Tensor wv1t, torch::Tensor bv1,
+                      torch::Tensor adv1, torch::Tensor val1, int64_t rows);
+void head_out_step(torch::Tensor adv1, torch::Tensor val1, torch::Tensor wa2t,
+                   torch::Tensor ba2, torch::Tensor wv2t, torch::Tensor bv2,
+                   torch::Tensor q, torch::Tensor greedy);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "r2d2_amd gfx950 HIP kernels";
     m.def("fused_double_q_loss", &fused_double_q_loss,
@@ -228,6 +242,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pad2dense", &pad2dense, "padded NHWC -> dense rows (+relu)");
     m.def("dense2pad_mask", &dense2pad_mask,
           "dense grad -> padded, masked by act>0 (relu backward)");
+    m.def("lstm_cell_step", &lstm_cell_step,
+          "fused single-step LSTM cell for actor inference: input-row "
+          "assembly, both gate GEMMs, bias, nonlinearities and cell update "
+          "in one launch; writes h1, c1 (f32) and hb = bf16(h1)",
+          py::arg("latent"), py::arg("last_action"), py::arg("last_reward"),
+          py::arg("h0"), py::arg("c0"), py::arg("wih_t"), py::arg("whh_t"),
+          py::arg("lstm_bias"), py::arg("h1"), py::arg("c1"), py::arg("hb"),
+          py::arg("units") = 0, py::arg("rows") = 0);
+    m.def("head_hidden_step", &head_hidden_step,
+          "both dueling-head 512 -> 512 ReLU hidden layers in one launch",
+          py::arg("hb"), py::arg("wa1t"), py::arg("ba1"), py::arg("wv1t"),
+          py::arg("bv1"), py::arg("adv1"), py::arg("val1"),
+          py::arg("rows") = 0);
+    m.def("head_out_step", &head_out_step,
+          "both dueling-head output layers + q = V + A - mean(A) + greedy "
+          "action (first index of the row maximum) in one launch");
     m.def("gather_pack", &gather_pack,
           "regenerate prepacked weights from the flat param buffer "
           "(index-map gather, one launch per dtype)");

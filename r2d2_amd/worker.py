@@ -1267,7 +1267,15 @@ class VectorActor:
             state.last_reward = self.lr_t
             state.hidden_state = (self.h_t, self.c_t)
             with torch.no_grad():
-                if self.hip_inf is not None:
+                if self.hip_inf is not None and self.cfg.fused_actor_step:
+                    # the kernel's greedy action equals q_cpu.argmax below
+                    # (first index on ties); the host argmax over the q
+                    # copy LocalBuffer needs anyway is cheaper than a
+                    # third device-to-host copy
+                    q, _, (h, c) = self.hip_inf.step(
+                        self.obs_t, self.la_t, self.lr_t,
+                        (self.h_t, self.c_t))
+                elif self.hip_inf is not None:
                     q, (h, c) = self.hip_inf.forward(
                         self.obs_t, self.la_t, self.lr_t,
                         (self.h_t, self.c_t))
