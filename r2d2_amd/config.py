@@ -78,6 +78,18 @@ class Config:
     # dueling-head kernels, three launches after the encoder) instead of
     # HipInference.forward; only read where the K15 path is active
     fused_actor_step: bool = False
+    # GPU replay stores ONE (H, W) frame per step instead of the whole
+    # C-frame stack (rows + C - 1 frames per block, not rows * C); the gather
+    # kernel rebuilds the HWC stacks, so the sampled batch is the same.  Needs
+    # observations that really are rolling frame stacks (replay/frame_dedup.py)
+    replay_frame_dedup: bool = False
+    # ingest checks is_frame_stack(block.obs) and raises ValueError before
+    # touching the store, so a non-stacking env is never silently altered
+    replay_dedup_verify: bool = True
+    # SyntheticAtariEnv draws one (H, W) frame per step and returns the
+    # rolling stack of the last C (first frame repeated at reset), as
+    # AtariEnv does; off, every step draws C unrelated channels
+    synthetic_frame_stack: bool = False
     log_interval: int = 10                       # seconds; reference: config.py (log_interval)
     metrics_path: Optional[str] = None           # JSONL metrics emit (None = console only)
     # host-replay persistence (elastic resume; the reference never saves
@@ -104,6 +116,16 @@ class Config:
         assert 0.0 < self.gamma <= 1.0
         assert self.forward_steps >= 1
         assert len(self.obs_shape) in (1, 3)
+        if self.replay_frame_dedup:
+            if len(self.obs_shape) != 3 or self.obs_shape[0] < 2:
+                raise ValueError(
+                    f"replay_frame_dedup needs a (C, H, W) obs_shape with "
+                    f"C >= 2 stacked frames, got {tuple(self.obs_shape)}")
+            if not self.gpu_replay:
+                raise ValueError(
+                    "replay_frame_dedup is a storage mode of the GPU replay: "
+                    "it needs gpu_replay=True (the host ReplayBuffer stores "
+                    "whole stacks)")
 
     # derived -------------------------------------------------------------
     @property
@@ -180,6 +202,26 @@ PRESETS = {
     "mspacman_b256": dict(
         game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
         action_dim=9, encoder="nature", gpu_replay=False, batch_size=256,
+    ),
+    # `mspacman` with the GPU replay in frame-once mode — the preset
+    # bench.py takes to time the dedup gather in the full learner loop.
+    # bench.py ingests RANDOM blocks, which are not frame stacks, so the
+    # ingest check is off here: the store then keeps obs[0, :C-1] and
+    # obs[:, C-1] and the learner trains on the stacks rebuilt from those
+    # (same shapes and work, other bytes).  gpu_replay=True only satisfies
+    # the flag's validation; bench.py builds its GpuReplayBuffer either way.
+    "mspacman_dedup": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=True,
+        replay_frame_dedup=True, replay_dedup_verify=False,
+    ),
+    # `mspacman_gpu_replay` storing frames once, with the synthetic env in
+    # frame-stack mode so its blocks pass the ingest check
+    "mspacman_gpu_replay_dedup": dict(
+        game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
+        action_dim=9, encoder="nature", gpu_replay=True, num_actors=256,
+        buffer_capacity=4_000_000, vector_actors=True, actor_device="cuda",
+        replay_frame_dedup=True, synthetic_frame_stack=True,
     ),
 }
 

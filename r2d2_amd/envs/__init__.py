@@ -18,6 +18,7 @@ def create_env(env_type=None, seed=None, **kwargs):
     if env_type == "cartpole":
         return CartPoleEnv(seed=seed)
     if env_type == "synthetic":
+        kwargs.setdefault("frame_stack", c.synthetic_frame_stack)
         return SyntheticAtariEnv(obs_shape=c.obs_shape, action_dim=c.action_dim,
                                  seed=seed, **kwargs)
     if env_type == "atari":

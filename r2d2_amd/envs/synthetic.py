@@ -8,6 +8,12 @@ moving blob whose position depends on the action history, episodic reward
 with sparse positive events, and geometric episode termination.  The shape,
 dtype, and timing behavior match what the data path must sustain; the
 "game" itself is synthetic (BASELINE.json benches on synthetic frames).
+
+``frame_stack=True`` makes the observation a real frame stack, as
+``AtariEnv`` produces: one (H, W) frame is drawn per step by the same
+base-plus-blob generator, and the observation is the rolling stack of the
+last C frames, the first frame repeated at reset.  Off (the default) the C
+channels of every observation are drawn independently, as before.
 """
 
 import numpy as np
@@ -15,8 +21,10 @@ import numpy as np
 
 class SyntheticAtariEnv:
     def __init__(self, obs_shape=(4, 84, 84), action_dim=9, mean_ep_len=600,
-                 seed=None):
+                 seed=None, frame_stack=False):
         self.obs_shape = tuple(obs_shape)
+        self.frame_stack = bool(frame_stack)
+        self._stack = None
         self.action_dim = action_dim
         self.mean_ep_len = mean_ep_len
         self.rng = np.random.default_rng(seed)
@@ -29,10 +37,20 @@ class SyntheticAtariEnv:
         c, h, w = self.obs_shape
         y, x = int(self._pos[0]) % (h - 8), int(self._pos[1]) % (w - 8)
         f[:, y:y + 8, x:x + 8] = 255
-        return f
+        if not self.frame_stack:
+            return f
+        # f is ONE (1, H, W) frame: roll it into the stack of the last C
+        if self._stack is None:
+            self._stack = np.repeat(f, c, axis=0)
+        else:
+            self._stack = np.concatenate([self._stack[1:], f], axis=0)
+        return self._stack.copy()
 
     def reset(self) -> np.ndarray:
         c, h, w = self.obs_shape
+        if self.frame_stack:
+            c = 1
+            self._stack = None
         self._base = (self.rng.integers(0, 64, size=(c, h, w))).astype(np.uint8)
         self._pos = np.array([h // 2, w // 2], dtype=np.int64)
         self.steps = 0

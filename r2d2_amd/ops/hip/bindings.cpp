@@ -34,6 +34,12 @@ std::vector<torch::Tensor> replay_gather_batch(
     torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
     torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
     int64_t max_learn, int64_t H, int64_t spb);
+std::vector<torch::Tensor> replay_gather_batch_dedup(
+    torch::Tensor obs_store, torch::Tensor la_store, torch::Tensor lr_store,
+    torch::Tensor act_store, torch::Tensor nsr_store, torch::Tensor gam_store,
+    torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
+    torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
+    int64_t max_learn, int64_t H, int64_t spb, int64_t C);
 
 // gemm_kernels.hip
 torch::Tensor gemm_bias_act(torch::Tensor A, torch::Tensor Wt,
@@ -166,6 +172,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "metadata (no host round trip per ragged batch)");
     m.def("replay_gather_batch", &replay_gather_batch,
           "On-device padded batch assembly from the GPU block store");
+    m.def("replay_gather_batch_dedup", &replay_gather_batch_dedup,
+          "replay_gather_batch from the frame-once store: one (H, W) frame "
+          "per step, obs_rows + C - 1 frames per slot; the (B, T, H*W*C) HWC "
+          "stacks are rebuilt in the gather");
     m.def("gemm_bias_act", &gemm_bias_act, "MFMA GEMM + bias + activation");
     m.def("gemm_dgrad", &gemm_dgrad,
           "MFMA GEMM backward-data (+ fused ReLU mask; optional dense "

@@ -97,6 +97,92 @@ __global__ void gather_frames_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Kernel B': padded sequence tensors from the frame-once store.
+//   The store keeps ONE (H, W) frame per step: slot `blk` holds
+//   obs_rows + C - 1 frames, the first C - 1 being the lead-in of the slot's
+//   first stack, so row r's stack is frames r .. r + C - 1 of its slot and
+//   r + c never leaves the slot.  grid.x = B * T as in Kernel B; each block
+//   rebuilds one HWC stack:
+//     obs_out[((b*T + t)*HW + p)*C + c] = frame[blk*(obs_rows+C-1) + r + c][p]
+//   kVec4 (C == 4, HW % 16 == 0): a thread loads 16 pixels of each of the
+//   four frames, transposes every 4x4 byte tile in registers (v_perm_b32) and
+//   stores 64 contiguous bytes.  Otherwise one byte per thread-iteration.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint4 interleave4(unsigned a, unsigned b,
+                                             unsigned c, unsigned d) {
+    // a..d: 4 pixels of frames 0..3 (byte k = pixel k).  v_perm_b32 picks
+    // bytes 0-3 from its SECOND operand and 4-7 from its first.
+    unsigned ab_lo = __builtin_amdgcn_perm(b, a, 0x05010400u);  // a0 b0 a1 b1
+    unsigned ab_hi = __builtin_amdgcn_perm(b, a, 0x07030602u);  // a2 b2 a3 b3
+    unsigned cd_lo = __builtin_amdgcn_perm(d, c, 0x05010400u);
+    unsigned cd_hi = __builtin_amdgcn_perm(d, c, 0x07030602u);
+    uint4 o;
+    o.x = __builtin_amdgcn_perm(cd_lo, ab_lo, 0x05040100u);     // a0 b0 c0 d0
+    o.y = __builtin_amdgcn_perm(cd_lo, ab_lo, 0x07060302u);     // a1 b1 c1 d1
+    o.z = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x05040100u);
+    o.w = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
+    return o;
+}
+
+template <bool kVec4>
+__global__ void gather_frames_stack_kernel(
+    const unsigned char* __restrict__ obs_store,  // (num_blocks, obs_rows+C-1, HW)
+    const unsigned char* __restrict__ la_store,   // (num_blocks, obs_rows)
+    const float* __restrict__ lr_store,           // (num_blocks, obs_rows)
+    const int* __restrict__ meta,                 // (5, B)
+    unsigned char* __restrict__ obs_out,          // (B, T, HW, C)
+    float* __restrict__ la_out,                   // (B, T, A)
+    float* __restrict__ lr_out,                   // (B, T)
+    int B, int T, int A, int C, long HW, long obs_rows, long num_blocks) {
+    int bt = blockIdx.x;
+    int b = bt / T, t = bt % T;
+    int burn = meta[0 * B + b], learn = meta[1 * B + b], fwd = meta[2 * B + b];
+    int obs_start = meta[3 * B + b];
+    int valid = burn + learn + fwd;
+    long g = (long)obs_start - burn + t;  // global row: slot*obs_rows + r
+    long out_bytes = HW * C;
+    unsigned char* dst = obs_out + ((long)b * T + t) * out_bytes;
+    // a row outside the store (corrupt metadata) pads like t >= valid
+    if (t < valid && g >= 0 && g < num_blocks * obs_rows) {
+        long blk = g / obs_rows, r = g % obs_rows;
+        const unsigned char* src =
+            obs_store + (blk * (obs_rows + C - 1) + r) * HW;
+        if (kVec4) {
+            for (long q = threadIdx.x; q < HW / 16; q += blockDim.x) {
+                uint4 f0 = *reinterpret_cast<const uint4*>(src + q * 16);
+                uint4 f1 = *reinterpret_cast<const uint4*>(src + HW + q * 16);
+                uint4 f2 = *reinterpret_cast<const uint4*>(src + 2 * HW + q * 16);
+                uint4 f3 = *reinterpret_cast<const uint4*>(src + 3 * HW + q * 16);
+                uint4* o = reinterpret_cast<uint4*>(dst + q * 64);
+                o[0] = interleave4(f0.x, f1.x, f2.x, f3.x);
+                o[1] = interleave4(f0.y, f1.y, f2.y, f3.y);
+                o[2] = interleave4(f0.z, f1.z, f2.z, f3.z);
+                o[3] = interleave4(f0.w, f1.w, f2.w, f3.w);
+            }
+        } else {
+            for (long o = threadIdx.x; o < out_bytes; o += blockDim.x) {
+                long p = o / C, c = o % C;
+                dst[o] = src[c * HW + p];
+            }
+        }
+        if (threadIdx.x < A)
+            la_out[((long)b * T + t) * A + threadIdx.x] =
+                (la_store[g] == threadIdx.x) ? 1.f : 0.f;
+        if (threadIdx.x == 0) lr_out[(long)b * T + t] = lr_store[g];
+    } else {
+        if (kVec4) {
+            for (long o = threadIdx.x * 16; o < out_bytes; o += blockDim.x * 16)
+                *reinterpret_cast<uint4*>(dst + o) = uint4{0, 0, 0, 0};
+        } else {
+            for (long o = threadIdx.x; o < out_bytes; o += blockDim.x)
+                dst[o] = 0;
+        }
+        if (threadIdx.x < A) la_out[((long)b * T + t) * A + threadIdx.x] = 0.f;
+        if (threadIdx.x == 0) lr_out[(long)b * T + t] = 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Kernel C: flat per-learning-step arrays + hidden states + repeated weights.
 //   grid over B * max_learn threads.
 // ---------------------------------------------------------------------------
@@ -244,6 +330,108 @@ std::vector<torch::Tensor> replay_gather_batch(
                        meta.data_ptr<int>(), obs_out.data_ptr<unsigned char>(),
                        la_out.data_ptr<float>(), lr_out.data_ptr<float>(),
                        B, (int)T, (int)A, frame_bytes, obs_rows, (int)spb);
+
+    int total = B * (int)max_learn;
+    hipLaunchKernelGGL(gather_flat_kernel, dim3((total + 255) / 256), dim3(256),
+                       0, stream.stream(), act_store.data_ptr<unsigned char>(),
+                       nsr_store.data_ptr<float>(), gam_store.data_ptr<float>(),
+                       hid_store.data_ptr<float>(), idx.data_ptr<long>(),
+                       meta.data_ptr<int>(), seg.data_ptr<int>(),
+                       weights.data_ptr<float>(), act_out.data_ptr<long>(),
+                       nsr_out.data_ptr<float>(), gam_out.data_ptr<float>(),
+                       w_out.data_ptr<float>(), hid_out.data_ptr<float>(),
+                       B, (int)max_learn, (int)H, block_len, (int)spb);
+
+    return {obs_out, la_out, lr_out, act_out, nsr_out, gam_out, w_out, hid_out};
+}
+
+// Frame-once store: same outputs as replay_gather_batch, the (B, T, HW*C)
+// HWC stacks rebuilt from single frames by gather_frames_stack_kernel.
+std::vector<torch::Tensor> replay_gather_batch_dedup(
+    torch::Tensor obs_store, torch::Tensor la_store, torch::Tensor lr_store,
+    torch::Tensor act_store, torch::Tensor nsr_store, torch::Tensor gam_store,
+    torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
+    torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
+    int64_t max_learn, int64_t H, int64_t spb, int64_t C) {
+    TORCH_CHECK(C >= 2 && C <= 8, "replay_gather_batch_dedup: C must be in "
+                "[2, 8], got ", C);
+    TORCH_CHECK(obs_store.is_cuda() && la_store.is_cuda() && lr_store.is_cuda()
+                && act_store.is_cuda() && nsr_store.is_cuda()
+                && gam_store.is_cuda() && hid_store.is_cuda() && idx.is_cuda()
+                && meta.is_cuda() && seg.is_cuda() && weights.is_cuda(),
+                "replay_gather_batch_dedup: every tensor must be on the GPU");
+    TORCH_CHECK(obs_store.dtype() == torch::kUInt8
+                && la_store.dtype() == torch::kUInt8
+                && act_store.dtype() == torch::kUInt8,
+                "replay_gather_batch_dedup: obs/la/act stores must be uint8");
+    TORCH_CHECK(lr_store.dtype() == torch::kFloat32
+                && nsr_store.dtype() == torch::kFloat32
+                && gam_store.dtype() == torch::kFloat32
+                && hid_store.dtype() == torch::kFloat32
+                && weights.dtype() == torch::kFloat32,
+                "replay_gather_batch_dedup: lr/nsr/gam/hid/weights must be "
+                "float32");
+    TORCH_CHECK(idx.dtype() == torch::kInt64 && meta.dtype() == torch::kInt32
+                && seg.dtype() == torch::kInt32,
+                "replay_gather_batch_dedup: idx int64, meta/seg int32");
+    TORCH_CHECK(obs_store.is_contiguous() && la_store.is_contiguous()
+                && lr_store.is_contiguous() && act_store.is_contiguous()
+                && nsr_store.is_contiguous() && gam_store.is_contiguous()
+                && hid_store.is_contiguous() && idx.is_contiguous()
+                && meta.is_contiguous() && seg.is_contiguous()
+                && weights.is_contiguous(),
+                "replay_gather_batch_dedup: every tensor must be contiguous");
+    TORCH_CHECK(obs_store.dim() == 3 && la_store.dim() == 2
+                && lr_store.dim() == 2 && act_store.dim() == 2);
+    TORCH_CHECK(obs_store.size(1) == la_store.size(1) + C - 1,
+                "replay_gather_batch_dedup: the frame store holds ",
+                obs_store.size(1), " frames per slot, expected obs_rows + C - 1"
+                " = ", la_store.size(1) + C - 1);
+    TORCH_CHECK(obs_store.size(0) == la_store.size(0)
+                && lr_store.sizes() == la_store.sizes()
+                && act_store.size(0) == la_store.size(0)
+                && nsr_store.sizes() == act_store.sizes()
+                && gam_store.sizes() == act_store.sizes(),
+                "replay_gather_batch_dedup: store shapes disagree");
+    int B = idx.size(0);
+    TORCH_CHECK(B >= 1 && B <= 1024, "replay_gather_batch_dedup: B must be in "
+                "[1, 1024], got ", B);
+    TORCH_CHECK(meta.dim() == 2 && meta.size(0) == 5 && meta.size(1) == B
+                && seg.numel() == B + 1 && weights.numel() == B);
+    TORCH_CHECK(T >= 1 && A >= 1 && A <= 256 && max_learn >= 1 && H >= 1
+                && spb >= 1);
+    TORCH_CHECK(hid_store.dim() == 2 && hid_store.size(1) == 2 * H
+                && hid_store.size(0) == la_store.size(0) * spb);
+    long num_blocks = obs_store.size(0);
+    long obs_rows = la_store.size(1);
+    long HW = obs_store.size(2);
+    long block_len = act_store.size(1);
+    bool vec4 = (C == 4);
+    if (vec4)
+        TORCH_CHECK(HW % 16 == 0, "replay_gather_batch_dedup: the C = 4 "
+                    "vector path needs H*W % 16 == 0, got ", HW);
+    auto u8 = obs_store.options();
+    auto f32 = lr_store.options();
+    auto i64 = idx.options();
+    auto obs_out = torch::empty({B, T, HW * C}, u8);
+    auto la_out = torch::empty({B, T, A}, f32);
+    auto lr_out = torch::empty({B, T}, f32);
+    long Rmax = (long)B * max_learn;
+    auto act_out = torch::empty({Rmax}, i64);
+    auto nsr_out = torch::empty({Rmax}, f32);
+    auto gam_out = torch::empty({Rmax}, f32);
+    auto w_out = torch::empty({Rmax}, f32);
+    auto hid_out = torch::empty({2, B, H}, f32);
+    auto stream = at::cuda::getCurrentCUDAStream();
+
+    auto frames = vec4 ? gather_frames_stack_kernel<true>
+                       : gather_frames_stack_kernel<false>;
+    hipLaunchKernelGGL(frames, dim3(B * (int)T), dim3(256), 0,
+                       stream.stream(), obs_store.data_ptr<unsigned char>(),
+                       la_store.data_ptr<unsigned char>(), lr_store.data_ptr<float>(),
+                       meta.data_ptr<int>(), obs_out.data_ptr<unsigned char>(),
+                       la_out.data_ptr<float>(), lr_out.data_ptr<float>(),
+                       B, (int)T, (int)A, (int)C, HW, obs_rows, num_blocks);
 
     int total = B * (int)max_learn;
     hipLaunchKernelGGL(gather_flat_kernel, dim3((total + 255) / 256), dim3(256),

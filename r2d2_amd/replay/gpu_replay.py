@@ -10,6 +10,12 @@ reference worker.py:247-256) never leave the GPU.
 
 Ingest takes host `Block`s (from CPU actors) through pinned staging buffers
 on a dedicated copy stream.
+
+With ``config.replay_frame_dedup`` the store keeps ONE (H, W) frame per step
+— rows + C - 1 frames per block instead of rows stacks of C
+(replay/frame_dedup.py) — and the gather kernel rebuilds the HWC stacks, so
+the sampled batch is the same in both modes at a quarter of the obs bytes in
+HBM, in pinned staging and over H2D.
 """
 
 from typing import Optional
@@ -19,6 +25,7 @@ import torch
 
 from .. import config as cfg
 from ..ops import hip_ops
+from .frame_dedup import frames_from_stacked, is_frame_stack
 
 
 class GpuReplayBuffer:
@@ -46,10 +53,26 @@ class GpuReplayBuffer:
         self.obs_rows = c.burn_in_steps + self.block_len + 1
         self.T = c.seq_len  # fixed padded length (burn+learn+fwd)
 
+        self.frame_dedup = bool(c.replay_frame_dedup)
+        self.dedup_verify = bool(c.replay_dedup_verify)
         dev = self.device
         nb, spb = self.num_blocks, self.spb
-        self.obs_store = torch.zeros(nb, self.obs_rows, self.frame_bytes,
-                                     dtype=torch.uint8, device=dev)
+        if self.frame_dedup:
+            # one frame per step: slot = (C - 1) lead-in frames of its first
+            # stack + one frame per row, so row r's stack is frames
+            # r .. r + C - 1 of its own slot
+            C = self.obs_shape[0]
+            assert C >= 2, "replay_frame_dedup needs stacked frames"
+            if C == 4 and (self.frame_bytes // C) % 16:
+                raise ValueError(
+                    "replay_frame_dedup: the C = 4 gather loads 16 pixels at "
+                    f"a time and needs H*W % 16 == 0, got {self.obs_shape}")
+            self.obs_store = torch.zeros(
+                nb, self.obs_rows + C - 1, self.frame_bytes // C,
+                dtype=torch.uint8, device=dev)
+        else:
+            self.obs_store = torch.zeros(nb, self.obs_rows, self.frame_bytes,
+                                         dtype=torch.uint8, device=dev)
         self.la_store = torch.zeros(nb, self.obs_rows, dtype=torch.uint8, device=dev)
         self.lr_store = torch.zeros(nb, self.obs_rows, dtype=torch.float32, device=dev)
         self.act_store = torch.zeros(nb, self.block_len, dtype=torch.uint8, device=dev)
@@ -84,7 +107,8 @@ class GpuReplayBuffer:
         # device work runs on the copy stream — the training stream never
         # waits on ingest (the sample stream fences on _ev_ingest instead)
         self._n_pin = 4
-        self._pin_obs = [torch.empty(self.obs_rows, self.obs_store.shape[-1],
+        self._pin_obs = [torch.empty(self.obs_store.shape[1],
+                                     self.obs_store.shape[-1],
                                      dtype=torch.uint8, pin_memory=True)
                          for _ in range(self._n_pin)]
         self._pin_ev = [torch.cuda.Event() for _ in range(self._n_pin)]
@@ -128,13 +152,29 @@ class GpuReplayBuffer:
         nseq = block.num_sequences
         dev = self.device
 
-        # store frames HWC (channels innermost) — the conv kernels are NHWC,
-        # so gathered batches feed conv1 with no device-side permute
-        obs_np = block.obs
-        if obs_np.ndim == 4:
-            obs_np = np.ascontiguousarray(obs_np.transpose(0, 2, 3, 1))
-        obs_flat = torch.from_numpy(obs_np.reshape(rows, -1))
-        assert obs_flat.dtype == torch.uint8
+        if self.frame_dedup:
+            # frame-once store: no transpose, rows + C - 1 frames written
+            # straight into the pinned buffer below; the gather kernel
+            # rebuilds the HWC stacks
+            assert block.obs.dtype == np.uint8
+            assert block.obs.shape[1:] == self.obs_shape
+            if self.dedup_verify and not is_frame_stack(block.obs):
+                raise ValueError(
+                    "replay_frame_dedup: the block's observations are not a "
+                    "rolling frame stack (obs[t+1, :-1] != obs[t, 1:]); "
+                    "storing frames once would alter them.  Use a frame-"
+                    "stacking env (synthetic_frame_stack=True) or turn "
+                    "replay_frame_dedup off")
+            nframes = rows + self.obs_shape[0] - 1
+        else:
+            # store frames HWC (channels innermost) — the conv kernels are
+            # NHWC, so gathered batches feed conv1 with no device-side permute
+            obs_np = block.obs
+            if obs_np.ndim == 4:
+                obs_np = np.ascontiguousarray(obs_np.transpose(0, 2, 3, 1))
+            obs_flat = torch.from_numpy(obs_np.reshape(rows, -1))
+            assert obs_flat.dtype == torch.uint8
+            nframes = rows
         # frames: host memcpy into the next rotating pinned buffer (waiting
         # only for THAT buffer's previous H2D, n_pin blocks ago), then every
         # device-side ingest op — H2D copies, metadata, tree update — runs
@@ -145,7 +185,13 @@ class GpuReplayBuffer:
         if self._pin_used[pi]:
             self._pin_ev[pi].synchronize()
         pin = self._pin_obs[pi]
-        pin[:rows].copy_(obs_flat)
+        if self.frame_dedup:
+            frames_from_stacked(
+                block.obs,
+                out=pin[:nframes].numpy().reshape(
+                    (nframes,) + self.obs_shape[1:]))
+        else:
+            pin[:rows].copy_(obs_flat)
         self._pin_used[pi] = True
 
         # per-sequence metadata (host side)
@@ -166,7 +212,8 @@ class GpuReplayBuffer:
         with torch.cuda.stream(self._copy_stream):
             # don't overwrite a slot an in-flight sample may be gathering
             self._copy_stream.wait_event(self._ev_sampled)
-            self.obs_store[slot, :rows].copy_(pin[:rows], non_blocking=True)
+            self.obs_store[slot, :nframes].copy_(pin[:nframes],
+                                                 non_blocking=True)
             self._pin_ev[pi].record(self._copy_stream)
             la_idx = torch.from_numpy(np.ascontiguousarray(
                 block.last_action.argmax(1).astype(np.uint8)))
@@ -233,10 +280,18 @@ class GpuReplayBuffer:
             meta, seg = self._ext.replay_gather_meta(
                 idx, self.burn_s, self.learn_s, self.fwd_s, self.obs_start_s,
                 self.learn_off_s, self.spb)
-            outs = self._ext.replay_gather_batch(
-                self.obs_store, self.la_store, self.lr_store, self.act_store,
-                self.nsr_store, self.gam_store, self.hid_store, idx, meta,
-                seg, weight, self.T, self.A, self.learn_len, self.H, self.spb)
+            if self.frame_dedup:
+                outs = self._ext.replay_gather_batch_dedup(
+                    self.obs_store, self.la_store, self.lr_store,
+                    self.act_store, self.nsr_store, self.gam_store,
+                    self.hid_store, idx, meta, seg, weight, self.T, self.A,
+                    self.learn_len, self.H, self.spb, self.obs_shape[0])
+            else:
+                outs = self._ext.replay_gather_batch(
+                    self.obs_store, self.la_store, self.lr_store,
+                    self.act_store, self.nsr_store, self.gam_store,
+                    self.hid_store, idx, meta, seg, weight, self.T, self.A,
+                    self.learn_len, self.H, self.spb)
             if B == self.batch_size:
                 self._pin_i ^= 1
                 meta_h = self._pin_meta[self._pin_i]
