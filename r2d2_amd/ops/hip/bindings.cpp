@@ -43,17 +43,18 @@ std::vector<torch::Tensor> replay_gather_batch_dedup(
 
 // gemm_kernels.hip
 torch::Tensor gemm_bias_act(torch::Tensor A, torch::Tensor Wt,
-                            torch::Tensor bias, int64_t act, bool out_f32);
+                            torch::Tensor bias, int64_t act, bool out_f32,
+                            int64_t path);
 torch::Tensor gemm_dgrad(torch::Tensor dY, torch::Tensor act_out,
                          torch::Tensor W, bool relu_mask, int64_t k_out,
-                         c10::optional<torch::Tensor> out_mask);
+                         c10::optional<torch::Tensor> out_mask, int64_t path);
 std::vector<torch::Tensor> gemm_wgrad(torch::Tensor dY, torch::Tensor act_out,
                                       torch::Tensor A, bool relu_mask,
-                                      bool want_bias);
+                                      bool want_bias, int64_t path);
 void gemm_wgrad_into(torch::Tensor dY, torch::Tensor act_out, torch::Tensor A,
                      bool relu_mask, torch::Tensor dW_out,
                      torch::Tensor db_out,
-                     int64_t kd0, int64_t kd1, int64_t kd2);
+                     int64_t kd0, int64_t kd1, int64_t kd2, int64_t path);
 
 // conv_kernels.hip
 torch::Tensor conv_fwd(torch::Tensor in, torch::Tensor Wt, torch::Tensor bias,
@@ -176,21 +177,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "replay_gather_batch from the frame-once store: one (H, W) frame "
           "per step, obs_rows + C - 1 frames per slot; the (B, T, H*W*C) HWC "
           "stacks are rebuilt in the gather");
-    m.def("gemm_bias_act", &gemm_bias_act, "MFMA GEMM + bias + activation");
+    // path: 0 automatic, 64 the unstaged 64x64 kernel, 6464 / 12864 the
+    // LDS-staged 64x64 / 128x64 instantiations (tests and tools force one)
+    m.def("gemm_bias_act", &gemm_bias_act, "MFMA GEMM + bias + activation",
+          pybind11::arg("A"), pybind11::arg("Wt"), pybind11::arg("bias"),
+          pybind11::arg("act"), pybind11::arg("out_f32"),
+          pybind11::arg("path") = 0);
     m.def("gemm_dgrad", &gemm_dgrad,
           "MFMA GEMM backward-data (+ fused ReLU mask; optional dense "
           "k_out-column output; optional fused output ReLU mask)",
           pybind11::arg("dY"), pybind11::arg("act_out"), pybind11::arg("W"),
           pybind11::arg("relu_mask"), pybind11::arg("k_out") = 0,
-          pybind11::arg("out_mask") = pybind11::none());
-    m.def("gemm_wgrad", &gemm_wgrad, "MFMA GEMM backward-weight (+ bias grad)");
+          pybind11::arg("out_mask") = pybind11::none(),
+          pybind11::arg("path") = 0);
+    // wgrad path: 0 automatic, 64 the 64x64 kernel, 12864 the 128x64 tile
+    m.def("gemm_wgrad", &gemm_wgrad, "MFMA GEMM backward-weight (+ bias grad)",
+          pybind11::arg("dY"), pybind11::arg("act_out"), pybind11::arg("A"),
+          pybind11::arg("relu_mask"), pybind11::arg("want_bias"),
+          pybind11::arg("path") = 0);
     m.def("gemm_wgrad_into", &gemm_wgrad_into,
           "GEMM backward-weight accumulated straight into .grad views "
           "(optional (d0,d1,d2)->(d2,d0,d1) k-axis store permutation)",
           pybind11::arg("dY"), pybind11::arg("act_out"), pybind11::arg("A"),
           pybind11::arg("relu_mask"), pybind11::arg("dW_out"),
           pybind11::arg("db_out"), pybind11::arg("kd0") = 0,
-          pybind11::arg("kd1") = 0, pybind11::arg("kd2") = 0);
+          pybind11::arg("kd1") = 0, pybind11::arg("kd2") = 0,
+          pybind11::arg("path") = 0);
     m.def("conv_fwd", &conv_fwd, "Implicit-GEMM MFMA conv forward (NHWC)");
     m.def("conv_dgrad_dense", &conv_dgrad_dense,
           "MFMA conv backward-data from dense pre-masked dY (bounds-checked "
