@@ -203,6 +203,17 @@ PRESETS = {
         game_name="MsPacman", env_type="synthetic", obs_shape=(4, 84, 84),
         action_dim=9, encoder="nature", gpu_replay=False, batch_size=256,
     ),
+    # `cartpole` on the HIP engine: the 512-wide MLP encoder and LSTM are the
+    # one vector-observation shape the engine serves (ops/engine.py
+    # mlp_config_error).  Host replay: the GPU replay stores uint8 frames only
+    "cartpole_hip": dict(
+        game_name="CartPole", env_type="cartpole", obs_shape=(4,),
+        action_dim=2, encoder="mlp", hidden_dim=512, mlp_hidden=512,
+        device="cuda", dtype="bf16", use_hip_kernels=True, gpu_replay=False,
+        buffer_capacity=40_000, learning_starts=2_000, block_length=40,
+        burn_in_steps=8, learning_steps=8, forward_steps=3,
+        training_steps=2_000, num_actors=2, amp=True,
+    ),
     # `mspacman` with the GPU replay in frame-once mode — the preset
     # bench.py takes to time the dedup gather in the full learner loop.
     # bench.py ingests RANDOM blocks, which are not frame stacks, so the

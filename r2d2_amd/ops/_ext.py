@@ -28,6 +28,7 @@ SOURCES = [
     os.path.join(SRC_DIR, "impala_kernels.hip"),
     os.path.join(SRC_DIR, "optim_kernels.hip"),
     os.path.join(SRC_DIR, "actor_step_kernels.hip"),
+    os.path.join(SRC_DIR, "mlp_kernels.hip"),
 ]
 
 _module = None

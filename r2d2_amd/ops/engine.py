@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import config as cfg
-from ..models.encoders import ImpalaCNN
+from ..models.encoders import ImpalaCNN, MLPEncoder
 from . import hip_ops
 from . import impala as impala_ops
 
@@ -38,6 +38,35 @@ def conv1_channels(encoder):
     the nature conv1 takes a 4-frame stack or the reference's single frame,
     the IMPALA kernels a 4-frame stack only."""
     return (1, 4) if encoder == "nature" else (4,)
+
+
+# the MLP encoder (vector observations) runs on the engine at one width: fc2
+# is then a 512 -> 512 shape the MFMA GEMMs serve, and fc1 takes the
+# observation width the mlp_in kernels are built for
+MLP_WIDTH = 512
+MLP_MAX_OBS = 16
+
+
+def mlp_config_error(c):
+    """None when the engine serves this MLP-encoder config, else a message
+    naming the violated limit."""
+    if c.hidden_dim != 512:
+        return f"hidden_dim must be 512, got {c.hidden_dim}"
+    if c.mlp_hidden != MLP_WIDTH:
+        return (f"mlp_hidden must be {MLP_WIDTH} (other widths keep the "
+                f"eager path), got {c.mlp_hidden}")
+    if len(c.obs_shape) != 1:
+        return (f"the mlp encoder takes 1-D observations, got obs_shape "
+                f"{tuple(c.obs_shape)}")
+    if not 1 <= c.obs_shape[0] <= MLP_MAX_OBS:
+        return (f"the observation width must be in 1..{MLP_MAX_OBS}, got "
+                f"{c.obs_shape[0]}")
+    return None
+
+
+def mlp_supported(c):
+    """Whether an encoder == "mlp" config runs on the HIP engine."""
+    return c.encoder == "mlp" and mlp_config_error(c) is None
 
 
 def _round_up(x, m):
@@ -178,11 +207,19 @@ class _NetPack:
         f32 = lambda t: t.detach().to(dev).float().contiguous()
 
         self.impala = isinstance(enc, ImpalaCNN)
+        self.mlp = isinstance(enc, MLPEncoder)
         if self.impala:
             if hasattr(self, "imp"):
                 self.imp.refresh()
             else:
                 self.imp = impala_ops.ImpalaPack(enc, dev, self.with_bwd)
+        elif self.mlp:
+            # fc1 stays f32 (the mlp_in kernels read it as it is); fc2 in
+            # the GEMMs' bf16 layouts, (N, K) forward and (K, N) dgrad
+            self.mw1, self.mb1 = f32(enc.fc1.weight), f32(enc.fc1.bias)
+            self.mw2t, self.mb2 = to_bf(enc.fc2.weight), f32(enc.fc2.bias)
+            if self.with_bwd:
+                self.mw2_kn = self.mw2t.t().contiguous()       # (512, 512)
         else:
             # convs: (COUT, CIN, KH, KW) -> (COUT, KH*KW*CIN)
             def pack_conv(conv):
@@ -230,7 +267,7 @@ class _NetPack:
 
         if self.with_bwd:
             # dgrad prepacks (W stored (K, N))
-            if not self.impala:
+            if not (self.impala or self.mlp):
                 self.wf_kn = self.wft.t().contiguous()         # (3136, 512)
             self.wih_kn = self.wih_t.t().contiguous()          # (kin_pad, 4H)
             self.whh_bwd = self.whh_t.t().contiguous()         # (H, 4H)
@@ -238,7 +275,7 @@ class _NetPack:
             self.wa2_kn = self.wa2t.t().contiguous()           # (512, PAD)
             self.wv1_kn = self.wv1t.t().contiguous()
             self.wv2_kn = self.wv2t.t().contiguous()
-            if self.impala:
+            if self.impala or self.mlp:
                 return
             # nature conv dgrad prepacks
             w3 = enc.conv3.weight.detach().to(dev)             # (64,64,3,3)
@@ -279,13 +316,19 @@ class HipNetworkEngine:
     def __init__(self, online_net, target_net, device, config=None):
         c = config or cfg.get()
         self.cfg = c
-        assert c.encoder in ("nature", "impala") and c.hidden_dim == 512, \
-            "HIP engine supports the nature/impala 512-hidden configs"
-        assert tuple(c.obs_shape[1:]) == (84, 84)
+        self.mlp = c.encoder == "mlp"
+        if self.mlp:
+            err = mlp_config_error(c)
+            if err is not None:
+                raise ValueError(f"HIP engine, mlp encoder: {err}")
+        else:
+            assert c.encoder in ("nature", "impala") and c.hidden_dim == 512, \
+                "HIP engine supports the nature/impala 512-hidden configs"
+            assert tuple(c.obs_shape[1:]) == (84, 84)
         check_batch_size(c.batch_size, "config.batch_size")
-        self.C = c.obs_shape[0]
+        self.C = c.obs_shape[0]      # channels, or the vector width D (mlp)
         self.impala = c.encoder == "impala"
-        assert self.C in conv1_channels(c.encoder), \
+        assert self.mlp or self.C in conv1_channels(c.encoder), \
             "conv1 kernels instantiated for 1 (nature only) or 4 input channels"
         self.A = c.action_dim
         self.H = 512
@@ -359,8 +402,9 @@ class HipNetworkEngine:
         # reset is a plain kernel now (zero_gridbar_kernel).
         self._graph = None
         self._graph_key = None
+        # (bypassed for the mlp encoder: never captured with it)
         self._use_graph = (os.environ.get("R2D2_HIP_GRAPH", "0") == "1"
-                           and not self.timing)
+                           and not self.timing and not self.mlp)
 
     def _mark(self, name):
         if self.timing:
@@ -394,8 +438,13 @@ class HipNetworkEngine:
     _fwd_band = os.environ.get("R2D2_CONV_FWD_BAND", "1") != "0"
 
     def _encoder_fwd(self, pack, obs_hwc_u8, want_stash=True):
-        """obs: (M, 84, 84, C) uint8 -> latent (M, 512) bf16 + stashes."""
+        """obs: (M, 84, 84, C) uint8 -> latent (M, 512) bf16 + stashes.
+        MLP encoder: obs is X (M, D) float32, the stash (X, A1)."""
         m = self.m
+        if self.mlp:
+            a1 = m.mlp_in_fwd(obs_hwc_u8, pack.mw1, pack.mb1)
+            latent = m.gemm_bias_act(a1, pack.mw2t, pack.mb2, 1, False)
+            return latent, (obs_hwc_u8, a1)
         if self.impala:
             return impala_ops.encoder_fwd(m, pack.imp, obs_hwc_u8, want_stash,
                                           xp=getattr(self, "_xp", None))
@@ -572,7 +621,14 @@ class HipNetworkEngine:
 
         # ---- inputs ----------------------------------------------------
         obs = batch.obs
-        if obs.shape[-1] == self.C and obs.shape[2] == 84:   # already HWC
+        if self.mlp:
+            # (B, T, D) float32 vector observations: X (M, D), no dequant
+            if obs.dtype != torch.float32 or tuple(obs.shape[2:]) != (self.C,):
+                raise TypeError(
+                    f"the mlp encoder takes (B, T, {self.C}) float32 "
+                    f"observations, got {tuple(obs.shape)} {obs.dtype}")
+            obs_hwc = obs.reshape(B * T, self.C).contiguous()
+        elif obs.shape[-1] == self.C and obs.shape[2] == 84:   # already HWC
             obs_hwc = obs.reshape(B * T, 84, 84, self.C)
         else:                                      # (B,T,C,84,84) -> NHWC
             obs_hwc = obs.permute(0, 1, 3, 4, 2).reshape(B * T, 84, 84, self.C)
@@ -699,6 +755,21 @@ class HipNetworkEngine:
         self._mark("lstm_wgrads")
 
         M = B * T
+        if self.mlp:
+            # fc2 dgrad with fc2's own relu mask (lat) on load and fc1's
+            # (A1) on store; both wgrads add straight into the .grad views
+            X, a1 = enc_stash
+            enc = net.encoder
+            d_a1 = m.gemm_dgrad(dlat, lat_o, ON.mw2_kn, True, 0, a1)
+            m.gemm_wgrad_into(dlat, lat_o, a1, True, enc.fc2.weight.grad,
+                              enc.fc2.bias.grad)
+            m.mlp_in_wgrad_into(d_a1, X, enc.fc1.weight.grad,
+                                enc.fc1.bias.grad)
+            self._mark("mlp_bwd")
+            if grad_hook is not None:
+                grad_hook("encoder")
+            self._mark("grad_write")
+            return loss.squeeze(0), prio
         if self.impala:
             impala_ops.encoder_bwd(m, ON.imp, enc_stash, dlat, lat_o)
             self._mark("conv_bwd")
@@ -780,9 +851,15 @@ class HipInference:
 
     def __init__(self, net, device, config=None):
         c = config or cfg.get()
-        assert c.encoder in ("nature", "impala") and c.hidden_dim == 512
-        assert (tuple(c.obs_shape[1:]) == (84, 84)
-                and c.obs_shape[0] in conv1_channels(c.encoder)), c.obs_shape
+        if c.encoder == "mlp":
+            err = mlp_config_error(c)
+            if err is not None:
+                raise ValueError(f"HipInference, mlp encoder: {err}")
+        else:
+            assert c.encoder in ("nature", "impala") and c.hidden_dim == 512
+            assert (tuple(c.obs_shape[1:]) == (84, 84)
+                    and c.obs_shape[0] in conv1_channels(c.encoder)), \
+                c.obs_shape
         self.cfg = c
         self.A = net.action_dim
         self.device = torch.device(device)
@@ -790,19 +867,30 @@ class HipInference:
         self.net = net
         self.pack = _NetPack(net, self.device, self.A, with_bwd=False)
         self.impala = self.pack.impala
+        self.mlp = self.pack.mlp
 
     def refresh(self):
         self.pack.refresh()
 
+    def _mlp_latent(self, obs):
+        """obs (E, D) float32 on device -> latent (E, 512) bf16."""
+        p = self.pack
+        a1 = self.m.mlp_in_fwd(obs.contiguous(), p.mw1, p.mb1)
+        return self.m.gemm_bias_act(a1, p.mw2t, p.mb2, 1, False)
+
     @torch.no_grad()
     def forward(self, obs_u8_nchw, last_action, last_reward, hidden):
         """obs: (E, C, 84, 84) u8 on device, C = the config's obs_shape[0]
-        (4, or 1 for the nature encoder); hidden: (h, c) each (1, E, 512)
-        f32.  Returns (q (E, A) f32, (h', c'))."""
+        (4, or 1 for the nature encoder) — for the mlp encoder (E, D)
+        float32; hidden: (h, c) each (1, E, 512) f32.  Returns (q (E, A) f32,
+        (h', c'))."""
         m = self.m
         E = obs_u8_nchw.shape[0]
-        obs_hwc = obs_u8_nchw.permute(0, 2, 3, 1).contiguous()
-        if self.impala:
+        obs_hwc = (None if self.mlp
+                   else obs_u8_nchw.permute(0, 2, 3, 1).contiguous())
+        if self.mlp:
+            lat = self._mlp_latent(obs_u8_nchw)
+        elif self.impala:
             lat, _ = impala_ops.encoder_fwd(m, self.pack.imp, obs_hwc, False)
         else:
             p = self.pack
@@ -845,8 +933,11 @@ class HipInference:
         storage."""
         m = self.m
         E = obs_u8_nchw.shape[0]
-        obs_hwc = obs_u8_nchw.permute(0, 2, 3, 1).contiguous()
-        if self.impala:
+        obs_hwc = (None if self.mlp
+                   else obs_u8_nchw.permute(0, 2, 3, 1).contiguous())
+        if self.mlp:
+            lat = self._mlp_latent(obs_u8_nchw)
+        elif self.impala:
             lat, _ = impala_ops.encoder_fwd(m, self.pack.imp, obs_hwc, False)
         else:
             p = self.pack

@@ -155,6 +155,11 @@ void head_out_step(torch::Tensor adv1, torch::Tensor val1, torch::Tensor wa2t,
                    torch::Tensor ba2, torch::Tensor wv2t, torch::Tensor bv2,
                    torch::Tensor q, torch::Tensor greedy);
 
+// mlp_kernels.hip
+torch::Tensor mlp_in_fwd(torch::Tensor X, torch::Tensor W1, torch::Tensor b1);
+void mlp_in_wgrad_into(torch::Tensor dA1, torch::Tensor X,
+                       torch::Tensor dW1_out, torch::Tensor db1_out);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "r2d2_amd gfx950 HIP kernels";
     m.def("fused_double_q_loss", &fused_double_q_loss,
@@ -280,6 +285,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("head_out_step", &head_out_step,
           "both dueling-head output layers + q = V + A - mean(A) + greedy "
           "action (first index of the row maximum) in one launch");
+    m.def("mlp_in_fwd", &mlp_in_fwd,
+          "MLP encoder first layer: A1 (M, 512) bf16 = relu(X (M, D) f32 . "
+          "W1 (512, D)^T + b1), 1 <= D <= 16, f32 accumulation",
+          py::arg("X"), py::arg("W1"), py::arg("b1"));
+    m.def("mlp_in_wgrad_into", &mlp_in_wgrad_into,
+          "MLP encoder first-layer weight gradient accumulated into .grad "
+          "views: dW1 (512, D) += dA1^T . X, db1 (512,) += column sums of "
+          "dA1 (bf16, already ReLU-masked)",
+          py::arg("dA1"), py::arg("X"), py::arg("dW1_out"),
+          py::arg("db1_out"));
     m.def("gather_pack", &gather_pack,
           "regenerate prepacked weights from the flat param buffer "
           "(index-map gather, one launch per dtype)");

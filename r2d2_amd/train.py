@@ -101,7 +101,12 @@ def train(seed: int = 0, restart_dead_actors: bool = True,
     use_gpu_replay = c.gpu_replay and torch.cuda.is_available()
     learner = Learner(batch_queue, priority_queue, model,
                       model_dir=model_dir)
-    if use_gpu_replay and c.use_hip_kernels:
+    # vector-observation configs the engine serves train on it over the HOST
+    # replay (the GPU replay stores uint8 frames only)
+    from .ops.engine import mlp_supported
+    mlp_engine = (mlp_supported(c) and c.device == "cuda"
+                  and torch.cuda.is_available())
+    if (use_gpu_replay or mlp_engine) and c.use_hip_kernels:
         learner.enable_hip_engine()
     if resume:
         path = (_latest_checkpoint(model_dir, c.game_name)

@@ -694,18 +694,20 @@ class Learner:
 
     def enable_hip_engine(self):
         """Switch to the gfx950 HIP kernels.  For the flagship nature/512
-        config the FULL forward/backward runs through the hand-written engine
-        (ops/engine.py); otherwise the fused loss/priority kernels are used
-        under the eager forward.  Raises if the extension is not built — on a
+        config (and impala, and the 512-wide mlp encoder on 1-D observations
+        of width <= 16) the FULL forward/backward runs through the
+        hand-written engine (ops/engine.py); otherwise the fused
+        loss/priority kernels are used under the eager forward.  Raises if the extension is not built — on a
         GPU box the native path must be the one that runs."""
         from .ops import hip_ops
         hip_ops.ext(required=True)
         self.hip_engine = True
         c = self.cfg
-        from .ops.engine import conv1_channels
-        if (c.encoder in ("nature", "impala") and c.hidden_dim == 512
-                and len(c.obs_shape) == 3
-                and c.obs_shape[0] in conv1_channels(c.encoder)
+        from .ops.engine import conv1_channels, mlp_supported
+        if (((c.encoder in ("nature", "impala") and c.hidden_dim == 512
+              and len(c.obs_shape) == 3
+              and c.obs_shape[0] in conv1_channels(c.encoder))
+             or mlp_supported(c))
                 and self.device.type == "cuda"):
             from .ops.engine import HipNetworkEngine, check_batch_size
             # fail here, not inside the extension at the first update
@@ -1201,15 +1203,21 @@ class VectorActor:
         self.max_episode_steps = c.max_episode_steps
         self.block_length = c.block_length
         H = c.hidden_dim
-        # batched device-side inference state
-        self.obs_t = torch.zeros((E,) + tuple(c.obs_shape), dtype=torch.uint8,
+        # batched device-side inference state.  1-D (vector) observations
+        # are float32 env states and stay float32 on their way to the
+        # policy; 3-D frame stacks are uint8
+        vec_obs = len(c.obs_shape) == 1
+        self.obs_t = torch.zeros((E,) + tuple(c.obs_shape),
+                                 dtype=torch.float32 if vec_obs
+                                 else torch.uint8,
                                  device=self.device)
         self.la_t = torch.zeros(E, self.action_dim, device=self.device)
         self.la_t[:, 0] = 1.0
         self.lr_t = torch.zeros(E, 1, device=self.device)
         self.h_t = torch.zeros(1, E, H, device=self.device)
         self.c_t = torch.zeros(1, E, H, device=self.device)
-        self._obs_host = np.zeros((E,) + tuple(c.obs_shape), dtype=np.uint8)
+        self._obs_host = np.zeros((E,) + tuple(c.obs_shape),
+                                  dtype=np.float32 if vec_obs else np.uint8)
         self.episode_steps = np.zeros(E, dtype=np.int64)
         # (env_idx, need_reset): blocks finished one tick late with the next
         # forward's bootstrap q; need_reset marks episode truncation at
@@ -1221,11 +1229,13 @@ class VectorActor:
         self.hip_inf = None
         self.weight_bus = weight_bus
         self._bus_ver = 0
-        from .ops.engine import conv1_channels
+        from .ops.engine import conv1_channels, mlp_supported
         if (self.device.type == "cuda" and c.use_hip_kernels
-                and c.encoder in ("nature", "impala") and c.hidden_dim == 512
-                and tuple(c.obs_shape[1:]) == (84, 84)
-                and c.obs_shape[0] in conv1_channels(c.encoder)):
+                and ((c.encoder in ("nature", "impala")
+                      and c.hidden_dim == 512
+                      and tuple(c.obs_shape[1:]) == (84, 84)
+                      and c.obs_shape[0] in conv1_channels(c.encoder))
+                     or mlp_supported(c))):
             from .ops.engine import HipInference
             self.hip_inf = HipInference(self.model, self.device)
             if self.weight_bus is not None:   # catch up if already published
