@@ -84,7 +84,6 @@ torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
 // lstm_kernels.hip
 torch::Tensor assemble_rin(torch::Tensor latent, torch::Tensor la,
                            torch::Tensor lr, int64_t kin_pad);
-void barrier_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks);
 void handoff_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks);
 void handoff_counter_bench(torch::Tensor barrier_ws, int64_t steps,
                            int64_t nblocks);
@@ -246,7 +245,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("barrier_ws"), py::arg("rows") = 0);
     m.def("assemble_rin", &assemble_rin,
           "fused LSTM-input row assembly (latent | action | reward | pad)");
-    m.def("barrier_bench", &barrier_bench, "grid barrier microbench");
     m.def("handoff_bench", &handoff_bench, "producer-flag handoff microbench");
     m.def("handoff_counter_bench", &handoff_counter_bench,
           "counter-aggregated handoff microbench");

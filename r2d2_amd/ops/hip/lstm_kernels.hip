@@ -5,13 +5,16 @@
 //
 // Structure (forward):
 // - X = rin @ W_ih^T + b precomputed for all (B, T) steps by the MFMA GEMM.
-// - Persistent launch, one workgroup per 16 hidden units x batch half
-//   (x2 networks in one launch = 128 workgroups; slice width and batch
-//   split are template parameters — 8-unit and quartered variants stay
-//   selectable for comparison).  W_hh slice and the cell state c stay
-//   LDS-resident for all T steps; each step bulk-stages the previous h
-//   into LDS with coalesced 16 B loads, runs the gate GEMM entirely out
-//   of LDS, and advances h/c with vectorized stores.
+// - Persistent launch, one workgroup per 16 hidden units x 32-row batch
+//   group (x2 networks in one launch = 128 workgroups at 64 rows; 32 rows
+//   and fewer run 8-unit slices over one 64-row group).  W_hh slice and
+//   the cell state c stay LDS-resident for all T steps; each step
+//   bulk-stages the previous h into LDS with coalesced 16 B loads, runs
+//   the gate GEMM entirely out of LDS, and advances h/c with vectorized
+//   stores.
+// - ONE kernel template per direction.  A batch above 64 rows is cut into
+//   passes of 64 or 128 rows inside the same launch (lstm_fwd_multi /
+//   lstm_bwd_multi); the 64-row entry points are its one-pass case.
 // - NO global barrier: the time index makes the h exchange naturally
 //   double-buffered, so each step is synchronized by PRODUCER FLAGS only
 //   (HIP guide §6 G16: plain h stores -> per-wave vmcnt drain ->
@@ -26,10 +29,11 @@
 //   copy h/c through unchanged.
 //
 // Backward (online net): reverse recurrence with the same counter protocol
-// on the dgates stream — one workgroup per 16 hidden units x batch QUARTER
-// (128 workgroups; measured faster than batch halves — the backward is
-// CU-coverage bound); the recurrent GEMM streams dgates_{t+1} through a
-// 4-deep register prefetch ring with the 4H reduction split across waves.
+// on the dgates stream — one workgroup per 16 hidden units x 16-row batch
+// QUARTER (128 workgroups; measured faster than batch halves — the backward
+// is CU-coverage bound; 33..48 rows run two 32-row halves); the recurrent
+// GEMM streams dgates_{t+1} through a 4-deep register prefetch ring with
+// the 4H reduction split across waves.
 // The bulk weight gradients (dW_hh, dW_ih, db) and dX are plain GEMMs
 // outside the kernel (gemm_wgrad / gemm_dgrad over B*T rows).
 //
@@ -155,469 +159,27 @@ __device__ __forceinline__ bool await_count(unsigned* ctr, unsigned target,
 }
 
 // layout of the workspace (int32 words): [0..255] counters/flags (group g
-// uses word g*32 — one cacheline apart), [256] poison, then legacy barrier
-// words
+// uses word g*32 — one cacheline apart), [256] poison
 struct GridBar {
     unsigned flags[LSTM_MAX_FLAGS];
     unsigned poison;
-    unsigned bucket[8];
-    unsigned top;
-    unsigned gen;
-    unsigned gen_b[8];
 };
 
-// legacy counter barrier, kept for the microbench / comparison
-__device__ __forceinline__ bool grid_barrier(GridBar* bar, unsigned epoch,
-                                             int nblocks) {
-    __syncthreads();
-    __shared__ unsigned ok_s;
-    if (threadIdx.x == 0) {
-        int b = blockIdx.x & 7;
-        int per = (nblocks + 7 - b) >> 3;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        unsigned prev = __hip_atomic_fetch_add(&bar->bucket[b], 1u,
-                                               __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-        if (prev == epoch * (unsigned)per - 1u) {
-            unsigned p2 = __hip_atomic_fetch_add(&bar->top, 1u,
-                                                 __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-            if (p2 == epoch * 8u - 1u)
-                __hip_atomic_store(&bar->gen, epoch, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-        unsigned ok = 1;
-        long spins = 0;
-        while (__hip_atomic_load(&bar->gen, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > (long)2e8) { ok = 0; break; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        ok_s = ok;
-    }
-    __syncthreads();
-    return ok_s != 0;
-}
-
 // ---------------------------------------------------------------------------
-// Forward
-// ---------------------------------------------------------------------------
-// BROWS: batch rows per workgroup.  64 = classic layout (whole batch).
-// 32 = batch-split: twice the workgroups, half the LDS staging per step,
-// flag groups per (net, half).
-// UNITS: hidden units per workgroup.  8 = classic; 16 halves the workgroup
-// count (half the handoff producers per counter group AND half the total
-// h re-read traffic) at twice the per-wg MFMA work — the per-step cost is
-// latency-dominated, so fewer/fatter workgroups win (measured; VERDICT r1
-// item 7).
-template <int H, int BROWS = 64, int UNITS = 8>
-__global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
-    const __hip_bfloat16* __restrict__ X0,    // (B, T, 4H)
-    const __hip_bfloat16* __restrict__ X1,    // or null
-    const __hip_bfloat16* __restrict__ Whh0,  // (4H, H) row-major
-    const __hip_bfloat16* __restrict__ Whh1,
-    const float* __restrict__ init0,          // (2, B, H): h0, c0
-    const float* __restrict__ init1,
-    const int* __restrict__ lens,             // (B,)
-    __hip_bfloat16* __restrict__ Hout0,       // (B, T+1, H)
-    __hip_bfloat16* __restrict__ Hout1,
-    float* __restrict__ Cout0,                // (B, T+1, H)
-    float* __restrict__ Cout1,
-    __hip_bfloat16* __restrict__ stash0,      // (B, T, 4H) post-nonlin gates
-    GridBar* bar, int B, int T, int nblocks, int nhalves) {
-    constexpr int WGS_PER_HALF = H / UNITS;
-    constexpr int GCOLS = 4 * UNITS;          // gate columns per wg
-    const int wgs_per_net = WGS_PER_HALF * nhalves;
-    const int net = blockIdx.x / wgs_per_net;
-    const int rem = blockIdx.x % wgs_per_net;
-    const int half = rem / WGS_PER_HALF;
-    const int wid = rem % WGS_PER_HALF;
-    const int u0 = wid * UNITS;
-    const int b0 = half * BROWS;
-    const int Bl = min(B - b0, BROWS);
-
-    const __hip_bfloat16* X = net ? X1 : X0;
-    const __hip_bfloat16* Whh = net ? Whh1 : Whh0;
-    const float* init = net ? init1 : init0;
-    __hip_bfloat16* Hout = net ? Hout1 : Hout0;
-    float* Cout = net ? Cout1 : Cout0;
-    __hip_bfloat16* stash = net ? nullptr : stash0;
-    unsigned* ctr = &bar->flags[(net * nhalves + half) * 32];
-
-    __shared__ __hip_bfloat16 s_whh[GCOLS][H + 8];
-    __shared__ __hip_bfloat16 s_h[BROWS][H + 8];
-    __shared__ float s_gates[BROWS][GCOLS + 4];
-    __shared__ float s_c[BROWS][UNITS];
-    __shared__ __hip_bfloat16 s_hrow[BROWS][UNITS];
-
-    for (int e = threadIdx.x * 8; e < GCOLS * H; e += blockDim.x * 8) {
-        int c = e / H;
-        int k = e % H;
-        int g = c / UNITS, j = c % UNITS;
-        lstore8(&s_whh[c][k],
-                load_bf16x8(Whh + (long)(g * H + u0 + j) * H + k));
-    }
-    // h0 -> Hout[:,0] (this wg's slice); c0 -> LDS-resident cell state
-    for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
-        int bl = p / UNITS, j = p % UNITS;
-        int b = b0 + bl;
-        int u = u0 + j;
-        Hout[((long)b * (T + 1)) * H + u] = f2bf(init[(long)b * H + u]);
-        Cout[((long)b * (T + 1)) * H + u] = init[((long)B + b) * H + u];
-        s_c[bl][j] = init[((long)B + b) * H + u];
-    }
-    publish_count(ctr);
-
-    const int wave = threadIdx.x / WAVE;
-    const int lane = threadIdx.x & (WAVE - 1);
-    // wave tiling over (BROWS rows x GCOLS cols):
-    //   GCOLS=32: 2x2 waves of 16x16xNFRAG; GCOLS=64: 4 col-waves, rows
-    //   split into BROWS/16 fragments per wave.
-    constexpr int NCW = GCOLS / 16;            // col fragments total
-    constexpr int NFRAG = (NCW == 4) ? BROWS / 16 : BROWS / 32;
-    const int wrow0 = (NCW == 4) ? 0 : (wave >> 1) * 16 * NFRAG;
-    const int wcol0 = (NCW == 4) ? wave * 16 : (wave & 1) * 16;
-    const int frow = lane & 15;
-    const int kseg = (lane >> 4) * 8;
-
-    constexpr int CHUNKS = (BROWS * H) / 8;
-
-    for (int t = 0; t < T; ++t) {
-        if (!await_count(ctr, (unsigned)WGS_PER_HALF * (t + 1),
-                         &bar->poison))
-            return;
-        // bulk-stage this half's h_prev (Bl x H) into LDS
-        {
-            const long base = (long)t * H;
-#pragma unroll
-            for (int e = threadIdx.x; e < CHUNKS; e += 256) {
-                int row = e / (H / 8);
-                int k8 = (e % (H / 8)) * 8;
-                bf16x8 v = (row < Bl)
-                    ? load_bf16x8(Hout + ((long)(b0 + row) * (T + 1))
-                                  * H + base + k8)
-                    : zero_bf16x8();
-                lstore8(&s_h[row][k8], v);
-            }
-        }
-        __syncthreads();
-
-        // gates = h_prev @ Whh_slice^T  (all-LDS MFMA)
-        f32x4 acc[NFRAG] = {};
-#pragma unroll
-        for (int k0 = 0; k0 < H; k0 += 32) {
-            bf16x8 bfr = load_bf16x8(&s_whh[wcol0 + frow][k0 + kseg]);
-#pragma unroll
-            for (int i = 0; i < NFRAG; ++i) {
-                bf16x8 afr =
-                    load_bf16x8(&s_h[wrow0 + i * 16 + frow][k0 + kseg]);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    afr, bfr, acc[i], 0, 0, 0);
-            }
-        }
-        {
-            int ccol = lane & 15;
-            int crow = (lane >> 4) * 4;
-#pragma unroll
-            for (int i = 0; i < NFRAG; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    s_gates[wrow0 + i * 16 + crow + r][wcol0 + ccol] = acc[i][r];
-        }
-        __syncthreads();
-        // + X[t] (vectorized), then nonlinearities + state advance
-        {
-            int row = threadIdx.x / 4;
-            int g = threadIdx.x % 4;
-            if (row < Bl) {
-#pragma unroll
-                for (int j8 = 0; j8 < UNITS; j8 += 8) {
-                    bf16x8 x8 = load_bf16x8(
-                        X + ((long)(b0 + row) * T + t) * 4 * H + g * H + u0
-                        + j8);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        s_gates[row][g * UNITS + j8 + j] += (float)x8[j];
-                }
-            }
-        }
-        __syncthreads();
-        for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
-            int b = p / UNITS, j = p % UNITS;
-            bool active = t < lens[b0 + b];
-            float i_ = 0.f, f_ = 0.f, g_ = 0.f, o_ = 0.f;
-            float c = s_c[b][j], h;
-            if (active) {
-                i_ = sigmoidf_(s_gates[b][0 * UNITS + j]);
-                f_ = sigmoidf_(s_gates[b][1 * UNITS + j]);
-                g_ = tanhf(s_gates[b][2 * UNITS + j]);
-                o_ = sigmoidf_(s_gates[b][3 * UNITS + j]);
-                c = f_ * c + i_ * g_;
-                h = o_ * tanhf(c);
-            } else {
-                h = (float)*(const __bf16*)&s_h[b][u0 + j];
-            }
-            s_c[b][j] = c;
-            *(__bf16*)&s_hrow[b][j] = (__bf16)h;
-            s_gates[b][0 * UNITS + j] = i_;
-            s_gates[b][1 * UNITS + j] = f_;
-            s_gates[b][2 * UNITS + j] = g_;
-            s_gates[b][3 * UNITS + j] = o_;
-        }
-        __syncthreads();
-        // vectorized writers: h slice, c, gate stash
-        {
-            int tid = threadIdx.x;
-            constexpr int H8 = UNITS / 8;        // 16-B pieces per h row
-            if (tid < 64 * H8) {
-                int b = tid / H8, piece = tid % H8;
-                if (b < Bl) {
-                    long off = ((long)(b0 + b) * (T + 1) + t + 1) * H + u0
-                               + piece * 8;
-                    lstore8(Hout + off, *reinterpret_cast<bf16x8*>(
-                        &s_hrow[b][piece * 8]));
-                }
-            } else if (tid >= 128) {
-                // c writers: threads [128, 256) cover BROWS rows x C4
-                // float4 pieces (BROWS*C4 <= 128 for both layouts)
-                int t2 = tid - 128;
-                constexpr int C4 = UNITS / 4;    // float4 pieces per c row
-                static_assert(BROWS * C4 <= 128, "c-writer thread budget");
-                int b = t2 / C4, ch = t2 % C4;
-                if (b < Bl) {
-                    long off = ((long)(b0 + b) * (T + 1) + t + 1) * H + u0
-                               + ch * 4;
-                    *reinterpret_cast<float4*>(Cout + off) =
-                        *reinterpret_cast<float4*>(&s_c[b][ch * 4]);
-                }
-            }
-        }
-        if (stash) {
-            int row = threadIdx.x / 4;
-            int g = threadIdx.x % 4;
-            if (row < Bl) {
-#pragma unroll
-                for (int j8 = 0; j8 < UNITS; j8 += 8) {
-                    bf16x8 v;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        v[j] = (__bf16)s_gates[row][g * UNITS + j8 + j];
-                    lstore8(stash + ((long)(b0 + row) * T + t) * 4 * H
-                            + g * H + u0 + j8, v);
-                }
-            }
-        }
-        publish_count(ctr);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Backward (online net).  H/16 wgs, each 16 hidden units; W_hh^T slice in
-// LDS; dgates_{t+1} streamed through LDS in 256-col pieces; vectorized row
-// staging of stash/C/dHext; flag hand-off on the dgates stream.
-// ---------------------------------------------------------------------------
-// BROWS as in lstm_fwd_kernel: 32 doubles the workgroup count (batch
-// halves with their own flag groups) and splits the recurrent GEMM's K
-// reduction across wave pairs.  UNITS=32 (with BROWS=32) halves the
-// workgroup count again — fewer/fatter workgroups, half the handoff
-// producers per counter, waves tile (row half x col half) at full K
-// (s_wb then holds 32 u-rows x 4H ~ 131 KB of the 160 KB LDS).
-template <int H, int BROWS = 64, int UNITS = 16>
-__global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
-    const __hip_bfloat16* __restrict__ stash,  // (B, T, 4H) i,f,g,o
-    const float* __restrict__ Cout,            // (B, T+1, H)
-    const __hip_bfloat16* __restrict__ Hout,   // (unused)
-    const float* __restrict__ dHext,           // (B, T, H) upstream
-    const __hip_bfloat16* __restrict__ Whh_bwd,// (H, 4H): W_hh^T row-major
-    const int* __restrict__ lens,
-    __hip_bfloat16* __restrict__ dgates,       // (B, T, 4H) out
-    GridBar* bar, int B, int T, int nblocks, int nhalves) {
-    constexpr int WGS = H / UNITS;
-    constexpr int KSPLIT = (UNITS == 16 && BROWS == 32) ? 2
-                           : (UNITS == 16 && BROWS <= 16) ? 4 : 1;
-    constexpr int NCWAVE = UNITS / 16;         // col fragments across waves
-    const int half = blockIdx.x / WGS;
-    const int wid = blockIdx.x % WGS;
-    const int u0 = wid * UNITS;
-    const int b0 = half * BROWS;
-    const int Bl = min(B - b0, BROWS);
-
-    __shared__ __hip_bfloat16 s_wb[UNITS][4 * H + 8];
-    __shared__ float s_dh[BROWS][UNITS + 1];
-    __shared__ float s_dc[BROWS][UNITS + 1];
-    __shared__ float s_rec[KSPLIT][BROWS][UNITS + 1];
-    __shared__ __hip_bfloat16 s_dgout[BROWS][4 * UNITS + 8];
-
-    unsigned* ctr = &bar->flags[half * 32];
-
-    for (int e = threadIdx.x * 8; e < UNITS * 4 * H; e += blockDim.x * 8) {
-        int c = e / (4 * H);
-        int k = e % (4 * H);
-        lstore8(&s_wb[c][k], load_bf16x8(Whh_bwd + (long)(u0 + c) * 4 * H + k));
-    }
-    for (int p = threadIdx.x; p < BROWS * UNITS; p += blockDim.x) {
-        s_dh[p / UNITS][p % UNITS] = 0.f;
-        s_dc[p / UNITS][p % UNITS] = 0.f;
-    }
-    publish_count(ctr);
-
-    const int wave = threadIdx.x / WAVE;
-    const int lane = threadIdx.x & (WAVE - 1);
-    // UNITS=16, KSPLIT=1: 4 waves x 16-row tiles, full-K.
-    // UNITS=16, KSPLIT=2: wave pairs split the 4H reduction.
-    // UNITS=32: waves tile (row half x col half), full-K.
-    const int wrow0 = (NCWAVE == 2) ? (wave >> 1) * 16
-                      : (KSPLIT == 4) ? 0
-                      : (KSPLIT == 1 ? wave : (wave & 1)) * 16;
-    const int wcol0 = (NCWAVE == 2) ? (wave & 1) * 16 : 0;
-    const int wk = (KSPLIT == 1) ? 0 : (KSPLIT == 4) ? wave : (wave >> 1);
-    const int frow = lane & 15;
-    const int kseg = (lane >> 4) * 8;
-    constexpr int NCHUNK = 4 * H / 32;
-    const int c0 = wk * (NCHUNK / KSPLIT);
-    const int cN = c0 + NCHUNK / KSPLIT;
-
-    for (int t = T - 1; t >= 0; --t) {
-        unsigned need = (unsigned)(T - t);   // pieces published for t+1
-        if (!await_count(ctr, (unsigned)WGS * need, &bar->poison)) return;
-        // rec(B,UNITS) = dgates_{t+1}(B,4H) @ s_wb^T with a 4-deep register
-        // prefetch ring on the dgates stream (loads stay in flight across
-        // MFMAs; no per-piece barriers)
-        if (t < T - 1) {
-            const int arow_l = wrow0 + frow;
-            const __hip_bfloat16* dgrow =
-                dgates + ((long)(b0 + arow_l) * T + t + 1) * 4 * H;
-            const bool rvalid = arow_l < Bl;
-            f32x4 acc = {};
-            bf16x8 a0 = rvalid ? load_bf16x8(dgrow + (c0 + 0) * 32 + kseg)
-                : zero_bf16x8();
-            bf16x8 a1 = rvalid ? load_bf16x8(dgrow + (c0 + 1) * 32 + kseg)
-                : zero_bf16x8();
-            bf16x8 a2 = rvalid ? load_bf16x8(dgrow + (c0 + 2) * 32 + kseg)
-                : zero_bf16x8();
-            bf16x8 a3 = rvalid ? load_bf16x8(dgrow + (c0 + 3) * 32 + kseg)
-                : zero_bf16x8();
-#pragma unroll 4
-            for (int kc = c0; kc < cN; kc += 4) {
-                bf16x8 b0 =
-                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 0) * 32 + kseg]);
-                bf16x8 b1 =
-                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 1) * 32 + kseg]);
-                bf16x8 b2 =
-                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 2) * 32 + kseg]);
-                bf16x8 b3 =
-                    load_bf16x8(&s_wb[wcol0 + frow][(kc + 3) * 32 + kseg]);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
-                if (kc + 4 < cN)
-                    a0 = rvalid ? load_bf16x8(dgrow + (kc + 4) * 32 + kseg)
-                        : zero_bf16x8();
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc, 0, 0, 0);
-                if (kc + 5 < cN)
-                    a1 = rvalid ? load_bf16x8(dgrow + (kc + 5) * 32 + kseg)
-                        : zero_bf16x8();
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc, 0, 0, 0);
-                if (kc + 6 < cN)
-                    a2 = rvalid ? load_bf16x8(dgrow + (kc + 6) * 32 + kseg)
-                        : zero_bf16x8();
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b3, acc, 0, 0, 0);
-                if (kc + 7 < cN)
-                    a3 = rvalid ? load_bf16x8(dgrow + (kc + 7) * 32 + kseg)
-                        : zero_bf16x8();
-            }
-            int ccol = lane & 15;
-            int crow = (lane >> 4) * 4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = wrow0 + crow + r;
-                if (row < BROWS) s_rec[wk][row][wcol0 + ccol] = acc[r];
-            }
-        }
-        __syncthreads();
-        for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
-            int b = p / UNITS, jl = p % UNITS;
-            int bg = b0 + b;
-            int u = u0 + jl;
-            float dh, dc_in;
-            bool last = (t == T - 1);
-            bool active_next = !last && ((t + 1) < lens[bg]);
-            float ext = dHext[((long)bg * T + t) * H + u];
-            float rec = s_rec[0][b][jl];
-#pragma unroll
-            for (int kk = 1; kk < KSPLIT; ++kk) rec += s_rec[kk][b][jl];
-            if (last) {
-                dh = ext;
-                dc_in = 0.f;
-            } else if (active_next) {
-                long so1 = ((long)bg * T + t + 1) * 4 * H + u;
-                float f_next = bf2f(stash[so1 + H]);
-                dh = ext + rec;
-                dc_in = s_dc[b][jl] * f_next;
-            } else {
-                dh = ext + s_dh[b][jl];
-                dc_in = s_dc[b][jl];
-            }
-            bool active = t < lens[bg];
-            long so = ((long)bg * T + t) * 4 * H + u;
-            float di = 0.f, df = 0.f, dg = 0.f, do_ = 0.f;
-            if (active) {
-                float i_ = bf2f(stash[so]);
-                float f_ = bf2f(stash[so + H]);
-                float g_ = bf2f(stash[so + 2 * H]);
-                float o_ = bf2f(stash[so + 3 * H]);
-                float tc = tanhf(Cout[((long)bg * (T + 1) + t + 1) * H + u]);
-                float c_prev = Cout[((long)bg * (T + 1) + t) * H + u];
-                float dc = dc_in + dh * o_ * (1.f - tc * tc);
-                di = dc * g_ * i_ * (1.f - i_);
-                df = dc * c_prev * f_ * (1.f - f_);
-                dg = dc * i_ * (1.f - g_ * g_);
-                do_ = dh * tc * o_ * (1.f - o_);
-                s_dh[b][jl] = dh;
-                s_dc[b][jl] = dc;
-            } else {
-                s_dh[b][jl] = dh;
-                s_dc[b][jl] = dc_in;
-            }
-            *(__bf16*)&s_dgout[b][0 * UNITS + jl] = (__bf16)di;
-            *(__bf16*)&s_dgout[b][1 * UNITS + jl] = (__bf16)df;
-            *(__bf16*)&s_dgout[b][2 * UNITS + jl] = (__bf16)dg;
-            *(__bf16*)&s_dgout[b][3 * UNITS + jl] = (__bf16)do_;
-        }
-        __syncthreads();
-        // vectorized dgates writes: thread (b, g) -> UNITS/8 x 16 B
-        {
-            int tid = threadIdx.x;
-            int b = tid / 4;
-            int g = tid % 4;
-            if (b < Bl) {
-#pragma unroll
-                for (int rep = 0; rep < UNITS / 8; ++rep) {
-                    long off = ((long)(b0 + b) * T + t) * 4 * H + g * H + u0
-                               + rep * 8;
-                    lstore8(dgates + off,
-                            *reinterpret_cast<bf16x8*>(
-                                &s_dgout[b][g * UNITS + rep * 8]));
-                }
-            }
-        }
-        publish_count(ctr);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Multi-pass kernels: batches above 64 rows in ONE launch.
+// The persistent kernels: one template per direction, any batch in ONE
+// launch.
 //
-// The batch is cut into passes of P rows (P = 64 or 128).  A workgroup owns
-// one (net, 16-unit slice, row group) of a pass and, after the T steps of
-// pass p, moves on to pass p+1 with its W_hh slice still in LDS — a host
-// loop of 64-row launches would reload all 128 x 66 KB of weights and run
-// a workspace reset per chunk.  Only the per-pass state is re-initialised
-// (s_c / Hout[:,0] forward, s_dh / s_dc backward).  Every pass, a partial
-// last one included, runs the layout a 64-row launch uses today (forward
-// BROWS=32, backward BROWS=16 / KSPLIT=4) with the same per-element
-// accumulation order, so every full 64-row chunk is bit-equal to lstm_fwd /
-// lstm_bwd on those rows.
+// The batch is cut into passes of P = ngroups * BROWS rows.  A workgroup
+// owns one (net, UNITS-wide slice, row group) of a pass and, after the T
+// steps of pass p, moves on to pass p+1 with its W_hh slice still in LDS —
+// a host loop of 64-row launches would reload all 128 x 66 KB of weights
+// and run a workspace reset per chunk.  Only the per-pass state is
+// re-initialised (s_c / Hout[:,0] forward, s_dh / s_dc backward).  A 64-row
+// launch (lstm_fwd / lstm_bwd) is the npasses == 1 case; every pass of a
+// larger batch, a partial last one included, runs the layout a 64-row
+// launch uses (forward BROWS=32, backward BROWS=16 / KSPLIT=4) with the
+// same per-element accumulation order, so every full 64-row chunk is
+// bit-equal to lstm_fwd / lstm_bwd on those rows.
 //
 // Handoff invariant.  The counters are zeroed once per launch and only ever
 // grow.  Each workgroup publishes T+1 times per pass (once after the pass
@@ -636,8 +198,20 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
 // Row groups past the end of the batch (Bl <= 0) write nothing but still
 // await and publish, like the empty quarters of a small batch.
 // ---------------------------------------------------------------------------
+
+// ---------------------------------------------------------------------------
+// Forward
+// ---------------------------------------------------------------------------
+// BROWS: batch rows per workgroup.  64 = the whole batch in one row group
+// (B <= 32).  32 = batch-split: twice the workgroups, half the LDS staging
+// per step, counter groups per (net, row group).
+// UNITS: hidden units per workgroup.  8 goes with BROWS=64; 16 halves the
+// workgroup count (half the handoff producers per counter group AND half
+// the total h re-read traffic) at twice the per-wg MFMA work — the per-step
+// cost is latency-dominated, so fewer/fatter workgroups win (measured;
+// VERDICT r1 item 7).
 template <int H, int BROWS, int UNITS>
-__global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
+__global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
     const __hip_bfloat16* __restrict__ X0,    // (B, T, 4H)
     const __hip_bfloat16* __restrict__ X1,    // or null
     const __hip_bfloat16* __restrict__ Whh0,  // (4H, H) row-major
@@ -652,8 +226,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
     __hip_bfloat16* __restrict__ stash0,      // (B, T, 4H) post-nonlin gates
     GridBar* bar, int B, int T, int ngroups, int npasses) {
     constexpr int WGS = H / UNITS;            // producers per counter group
-    constexpr int GCOLS = 4 * UNITS;
-    static_assert(GCOLS == 64, "wave tiling below is the 4-col-wave layout");
+    constexpr int GCOLS = 4 * UNITS;          // gate columns per wg
     const int wgs_per_net = WGS * ngroups;
     const int net = blockIdx.x / wgs_per_net;
     const int rem = blockIdx.x % wgs_per_net;
@@ -687,10 +260,16 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
 
     const int wave = threadIdx.x / WAVE;
     const int lane = threadIdx.x & (WAVE - 1);
-    constexpr int NFRAG = BROWS / 16;
-    const int wcol0 = wave * 16;
+    // wave tiling over (BROWS rows x GCOLS cols):
+    //   GCOLS=32: 2x2 waves of 16x16xNFRAG; GCOLS=64: 4 col-waves, rows
+    //   split into BROWS/16 fragments per wave.
+    constexpr int NCW = GCOLS / 16;            // col fragments total
+    constexpr int NFRAG = (NCW == 4) ? BROWS / 16 : BROWS / 32;
+    const int wrow0 = (NCW == 4) ? 0 : (wave >> 1) * 16 * NFRAG;
+    const int wcol0 = (NCW == 4) ? wave * 16 : (wave & 1) * 16;
     const int frow = lane & 15;
     const int kseg = (lane >> 4) * 8;
+
     constexpr int CHUNKS = (BROWS * H) / 8;
 
     for (int pass = 0; pass < npasses; ++pass) {
@@ -736,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
 #pragma unroll
                 for (int i = 0; i < NFRAG; ++i) {
                     bf16x8 afr =
-                        load_bf16x8(&s_h[i * 16 + frow][k0 + kseg]);
+                        load_bf16x8(&s_h[wrow0 + i * 16 + frow][k0 + kseg]);
                     acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         afr, bfr, acc[i], 0, 0, 0);
                 }
@@ -748,7 +327,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
                 for (int i = 0; i < NFRAG; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        s_gates[i * 16 + crow + r][wcol0 + ccol] = acc[i][r];
+                        s_gates[wrow0 + i * 16 + crow + r][wcol0 + ccol] =
+                            acc[i][r];
             }
             __syncthreads();
             // + X[t] (vectorized), then nonlinearities + state advance
@@ -759,8 +339,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
 #pragma unroll
                     for (int j8 = 0; j8 < UNITS; j8 += 8) {
                         bf16x8 x8 = load_bf16x8(
-                            X + ((long)(b0 + row) * T + t) * 4 * H + g * H
-                            + u0 + j8);
+                            X + ((long)(b0 + row) * T + t) * 4 * H + g * H + u0
+                            + j8);
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
                             s_gates[row][g * UNITS + j8 + j] += (float)x8[j];
@@ -798,20 +378,21 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
                 if (tid < 64 * H8) {
                     int b = tid / H8, piece = tid % H8;
                     if (b < Bl) {
-                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H
-                                   + u0 + piece * 8;
+                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H + u0
+                                   + piece * 8;
                         lstore8(Hout + off, *reinterpret_cast<bf16x8*>(
                             &s_hrow[b][piece * 8]));
                     }
-                } else {
+                } else if (tid >= 128) {
+                    // c writers: threads [128, 256) cover BROWS rows x C4
+                    // float4 pieces (BROWS*C4 <= 128 for both layouts)
                     int t2 = tid - 128;
                     constexpr int C4 = UNITS / 4;  // float4 pieces per c row
                     static_assert(BROWS * C4 <= 128, "c-writer thread budget");
-                    static_assert(64 * H8 == 128, "h writers fill [0, 128)");
                     int b = t2 / C4, ch = t2 % C4;
                     if (b < Bl) {
-                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H
-                                   + u0 + ch * 4;
+                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H + u0
+                                   + ch * 4;
                         *reinterpret_cast<float4*>(Cout + off) =
                             *reinterpret_cast<float4*>(&s_c[b][ch * 4]);
                     }
@@ -837,8 +418,16 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_multi_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Backward (online net).  H/16 wgs per row group, each 16 hidden units;
+// W_hh^T slice in LDS; dgates_{t+1} streamed from global through a register
+// ring; counter hand-off on the dgates stream.
+// ---------------------------------------------------------------------------
+// BROWS: 16 = batch quarters, all four waves on one 16-row tile, each with
+// a quarter of the recurrent GEMM's 4H reduction (KSPLIT 4).  32 = batch
+// halves: waves tile (row half x K half) (KSPLIT 2).
 template <int H, int BROWS, int UNITS>
-__global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
+__global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
     const __hip_bfloat16* __restrict__ stash,  // (B, T, 4H) i,f,g,o
     const float* __restrict__ Cout,            // (B, T+1, H)
     const float* __restrict__ dHext,           // (B, T, H) upstream
@@ -846,9 +435,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
     const int* __restrict__ lens,
     __hip_bfloat16* __restrict__ dgates,       // (B, T, 4H) out
     GridBar* bar, int B, int T, int ngroups, int npasses) {
-    static_assert(BROWS == 16 && UNITS == 16, "the KSPLIT=4 quarter layout");
+    static_assert(UNITS == 16 && (BROWS == 16 || BROWS == 32),
+                  "one 16-col MFMA tile; 4 waves = BROWS/16 row tiles x KSPLIT");
     constexpr int WGS = H / UNITS;
-    constexpr int KSPLIT = 4;
+    constexpr int KSPLIT = 64 / BROWS;
     const int grp = blockIdx.x / WGS;
     const int wid = blockIdx.x % WGS;
     const int u0 = wid * UNITS;
@@ -871,7 +461,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
 
     const int wave = threadIdx.x / WAVE;
     const int lane = threadIdx.x & (WAVE - 1);
-    const int wk = wave;                       // this wave's quarter of 4H
+    const int wrow0 = (KSPLIT == 4) ? 0 : (wave & 1) * 16;
+    const int wk = (KSPLIT == 4) ? wave : (wave >> 1);  // this wave's K part
     const int frow = lane & 15;
     const int kseg = (lane >> 4) * 8;
     constexpr int NCHUNK = 4 * H / 32;
@@ -893,10 +484,11 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
             if (!await_count(ctr, (unsigned)WGS * (base_pub + need),
                              &bar->poison))
                 return;
-            // rec(B,UNITS) = dgates_{t+1}(B,4H) @ s_wb^T, 4-deep register
-            // prefetch ring on the dgates stream
+            // rec(B,UNITS) = dgates_{t+1}(B,4H) @ s_wb^T with a 4-deep register
+            // prefetch ring on the dgates stream (loads stay in flight across
+            // MFMAs; no per-piece barriers)
             if (t < T - 1) {
-                const int arow_l = frow;
+                const int arow_l = wrow0 + frow;
                 const __hip_bfloat16* dgrow =
                     dgates + ((long)(b0 + arow_l) * T + t + 1) * 4 * H;
                 const bool rvalid = arow_l < Bl;
@@ -936,7 +528,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
                 int crow = (lane >> 4) * 4;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    s_rec[wk][crow + r][ccol] = acc[r];
+                    s_rec[wk][wrow0 + crow + r][ccol] = acc[r];
             }
             __syncthreads();
             for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
@@ -997,8 +589,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_multi_kernel(
                 if (b < Bl) {
 #pragma unroll
                     for (int rep = 0; rep < UNITS / 8; ++rep) {
-                        long off = ((long)(b0 + b) * T + t) * 4 * H + g * H
-                                   + u0 + rep * 8;
+                        long off = ((long)(b0 + b) * T + t) * 4 * H + g * H + u0
+                                   + rep * 8;
                         lstore8(dgates + off,
                                 *reinterpret_cast<bf16x8*>(
                                     &s_dgout[b][g * UNITS + rep * 8]));
@@ -1070,12 +662,6 @@ __global__ __launch_bounds__(256) void assemble_rin_kernel(
     *reinterpret_cast<bf16x8*>(rin + idx) = v;
 }
 
-// barrier-only microbench
-__global__ void barrier_bench_kernel(GridBar* bar, int steps, int nblocks) {
-    for (int t = 0; t < steps; ++t)
-        if (!grid_barrier(bar, (unsigned)(t + 1), nblocks)) return;
-}
-
 // handoff-only microbench: prices one flag publish/await round at `nblocks`
 __global__ void handoff_bench_kernel(GridBar* bar, int steps, int nblocks) {
     unsigned* flags = bar->flags;
@@ -1130,15 +716,6 @@ torch::Tensor assemble_rin(torch::Tensor latent, torch::Tensor la,
     return rin;
 }
 
-void barrier_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks) {
-    auto stream = at::cuda::getCurrentCUDAStream();
-    zero_ws(barrier_ws, stream.stream());
-    hipLaunchKernelGGL(barrier_bench_kernel, dim3((int)nblocks), dim3(256), 0,
-                       stream.stream(),
-                       reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),
-                       (int)steps, (int)nblocks);
-}
-
 void handoff_counter_bench(torch::Tensor barrier_ws, int64_t steps,
                            int64_t nblocks) {
     auto stream = at::cuda::getCurrentCUDAStream();
@@ -1173,168 +750,24 @@ static void lstm_check(const torch::Tensor& t, const char* name,
                 t.sizes());
 }
 
-std::vector<torch::Tensor> lstm_fwd(
-    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
-    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
-    torch::Tensor barrier_ws, bool want_stash) {
-    TORCH_CHECK(X0.is_cuda() && X0.dtype() == torch::kBFloat16 && X0.is_contiguous());
-    TORCH_CHECK(X0.dim() == 3, "X0 must be (B, T, 4H)");
-    long B = X0.size(0), T = X0.size(1);
-    long H4 = X0.size(2);
-    long H = H4 / 4;
-    TORCH_CHECK(H4 == 2048, "lstm_fwd is instantiated for H=512");
-    TORCH_CHECK(B >= 1 && B <= 64, "1 <= B <= 64 per launch");
-    bool two = X1.defined() && X1.numel() > 0;
-    lstm_check(Whh0, "Whh0", torch::kBFloat16, {H4, H});
-    lstm_check(init0, "init0", torch::kFloat32, {2, B, H});
-    lstm_check(lens, "lens", torch::kInt32, {B});
-    if (two) {
-        lstm_check(X1, "X1", torch::kBFloat16, {B, T, H4});
-        lstm_check(Whh1, "Whh1", torch::kBFloat16, {H4, H});
-        lstm_check(init1, "init1", torch::kFloat32, {2, B, H});
-    }
 
-    auto bf = X0.options();
-    auto f32 = X0.options().dtype(torch::kFloat32);
-    auto H0 = torch::empty({B, T + 1, H}, bf);
-    auto C0 = torch::empty({B, T + 1, H}, f32);
-    auto H1 = two ? torch::empty({B, T + 1, H}, bf) : torch::Tensor();
-    auto C1 = two ? torch::empty({B, T + 1, H}, f32) : torch::Tensor();
-    auto stash = want_stash ? torch::empty({B, T, H4}, bf) : torch::Tensor();
-
-    // UNITS: hidden units per workgroup.  16 is the measured default for
-    // the dual-net batch-split launch (fewer/fatter workgroups: half the
-    // handoff producers per counter and half the total h re-read);
-    // R2D2_LSTM_UNITS=8 selects the classic layout for comparison.
-    static const int units_env = [] {
-        const char* e = getenv("R2D2_LSTM_UNITS");
-        return e ? atoi(e) : 16;
-    }();
-    // R2D2_LSTM_FWD_BROWS=16 quarters the batch (256 wgs for the dual-net
-    // launch = every CU)
-    static const int fbrows_env = [] {
-        const char* e = getenv("R2D2_LSTM_FWD_BROWS");
-        return e ? atoi(e) : 32;
-    }();
-    int units = (units_env == 8) ? 8 : 16;
-    int nhalves = B > 32 ? 2 : 1;
-    if (nhalves == 1) units = 8;   // single-half keeps the classic layout
-    int fbrows = (nhalves == 2 && units == 16 && fbrows_env == 16 && B > 48)
-                     ? 16 : (nhalves == 2 ? 32 : 64);
-    if (fbrows == 16) nhalves = 4;
-    int wgs = (int)H / units;
-    int nblocks = wgs * (two ? 2 : 1) * nhalves;
-    auto stream = at::cuda::getCurrentCUDAStream();
-    zero_ws(barrier_ws, stream.stream());
-
-    auto bp = [](torch::Tensor& t) {
-        return t.defined()
-            ? reinterpret_cast<__hip_bfloat16*>(t.data_ptr()) : nullptr;
-    };
-#define LSTMF(BROWS_, UNITS_)                                                 \
-    hipLaunchKernelGGL((lstm_fwd_kernel<512, BROWS_, UNITS_>), dim3(nblocks), \
-        dim3(256), 0, stream.stream(),                                        \
-        reinterpret_cast<const __hip_bfloat16*>(X0.data_ptr()),               \
-        two ? reinterpret_cast<const __hip_bfloat16*>(X1.data_ptr()) : nullptr,\
-        reinterpret_cast<const __hip_bfloat16*>(Whh0.data_ptr()),             \
-        two ? reinterpret_cast<const __hip_bfloat16*>(Whh1.data_ptr()) : nullptr,\
-        init0.data_ptr<float>(),                                              \
-        two ? init1.data_ptr<float>() : nullptr,                              \
-        lens.data_ptr<int>(), bp(H0), bp(H1),                                 \
-        C0.data_ptr<float>(), two ? C1.data_ptr<float>() : nullptr,           \
-        want_stash ? bp(stash) : nullptr,                                     \
-        reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),                    \
-        (int)B, (int)T, nblocks, nhalves)
-    if (fbrows == 16) LSTMF(16, 16);
-    else if (nhalves == 2) {
-        if (units == 16) LSTMF(32, 16); else LSTMF(32, 8);
-    } else {
-        LSTMF(64, 8);
-    }
-#undef LSTMF
-
-    std::vector<torch::Tensor> out = {H0, C0};
-    out.push_back(two ? H1 : torch::Tensor());
-    out.push_back(two ? C1 : torch::Tensor());
-    out.push_back(want_stash ? stash : torch::Tensor());
-    return out;
-}
-
-torch::Tensor lstm_bwd(torch::Tensor stash, torch::Tensor Cout,
-                       torch::Tensor Hout, torch::Tensor dHext,
-                       torch::Tensor Whh_bwd, torch::Tensor lens,
-                       torch::Tensor barrier_ws) {
-    TORCH_CHECK(stash.defined() && stash.dim() == 3,
-                "stash must be (B, T, 4H)");
-    long B = stash.size(0), T = stash.size(1), H4 = stash.size(2);
-    long H = H4 / 4;
-    TORCH_CHECK(H4 == 2048, "lstm_bwd is instantiated for H=512");
-    // every layout below covers at most 64 rows (4 quarters of 16): rows
-    // past that would come back unwritten from torch::empty
-    TORCH_CHECK(B >= 1 && B <= 64, "1 <= B <= 64 per launch");
-    lstm_check(stash, "stash", torch::kBFloat16, {B, T, H4});
-    lstm_check(Cout, "Cout", torch::kFloat32, {B, T + 1, H});
-    lstm_check(Hout, "Hout", torch::kBFloat16, {B, T + 1, H});
-    lstm_check(dHext, "dHext", torch::kFloat32, {B, T, H});
-    lstm_check(Whh_bwd, "Whh_bwd", torch::kBFloat16, {H, H4});
-    lstm_check(lens, "lens", torch::kInt32, {B});
-    auto dgates = torch::empty({B, T, H4}, stash.options());
-    // Measured DEAD END (docs/KERNELS.md): 32-unit bwd slices
-    // (R2D2_LSTM_BWD_UNITS=32) run 1.34 ms vs 0.94 ms at 16 — the 131 KB
-    // s_wb slab and the narrower 16-row dgates A-tiles at full K=2048 cost
-    // more than the halved handoff saves.  16 stays the default (the fwd
-    // kernel, whose weight slab is 4x smaller, DOES win at 16 units).
-    static const int bunits_env = [] {
-        const char* e = getenv("R2D2_LSTM_BWD_UNITS");
-        return e ? atoi(e) : 16;
-    }();
-    // batch QUARTERED by default (128 wgs, KSPLIT=4): measured 0.71 vs
-    // 0.95 ms at BROWS=32 (the backward is CU-coverage bound).  Pushing
-    // further to BROWS=8 (256 wgs) LOSES (12.03k vs 12.43k end-to-end) —
-    // 8-row batches leave the 16-row MFMA A-fragments half empty.
-    // R2D2_LSTM_BWD_BROWS selects 8/16/32 for comparison.
-    static const int brows_env = [] {
-        const char* e = getenv("R2D2_LSTM_BWD_BROWS");
-        return e ? atoi(e) : 16;
-    }();
-    int nhalves = B > 32 ? 2 : 1;
-    int units = (nhalves == 2 && bunits_env == 32) ? 32 : 16;
-    int brows = (nhalves == 2 && units == 16 && B > 48)
-                    ? brows_env : (nhalves == 2 ? 32 : 64);
-    if (brows != 8 && brows != 16 && brows != 32) brows = 16;
-    if (brows == 16) nhalves = 4;
-    else if (brows == 8) nhalves = 8;
-    int nblocks = (int)H / units * nhalves;
-    auto stream = at::cuda::getCurrentCUDAStream();
-    zero_ws(barrier_ws, stream.stream());
-#define LSTMB(BROWS_, UNITS_)                                                 \
-    hipLaunchKernelGGL((lstm_bwd_kernel<512, BROWS_, UNITS_>), dim3(nblocks), \
-        dim3(256), 0, stream.stream(),                                        \
-        reinterpret_cast<const __hip_bfloat16*>(stash.data_ptr()),            \
-        Cout.data_ptr<float>(),                                               \
-        reinterpret_cast<const __hip_bfloat16*>(Hout.data_ptr()),             \
-        dHext.data_ptr<float>(),                                              \
-        reinterpret_cast<const __hip_bfloat16*>(Whh_bwd.data_ptr()),          \
-        lens.data_ptr<int>(),                                                 \
-        reinterpret_cast<__hip_bfloat16*>(dgates.data_ptr()),                 \
-        reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),                    \
-        (int)B, (int)T, nblocks, nhalves)
-    if (brows == 8) LSTMB(8, 16);
-    else if (brows == 16) LSTMB(16, 16);
-    else if (nhalves == 2) {
-        if (units == 32) LSTMB(32, 32); else LSTMB(32, 16);
-    } else {
-        LSTMB(64, 16);
-    }
-#undef LSTMB
-    return dgates;
+static void lstm_check_ws(const torch::Tensor& ws) {
+    TORCH_CHECK(ws.defined() && ws.is_cuda() && ws.is_contiguous()
+                && ws.scalar_type() == torch::kInt32
+                && ws.numel() * 4 >= (long)sizeof(GridBar),
+                "barrier_ws must be a contiguous CUDA int32 tensor of >= ",
+                sizeof(GridBar) / 4, " words");
 }
 
 // ---------------------------------------------------------------------------
-// Multi-pass entry points (1 <= B <= 256).  `rows` is the pass size P: 64
-// (128 workgroups, today's grid) or 128 (256 workgroups); 0 takes
-// R2D2_LSTM_MULTI_ROWS, default LSTM_MULTI_ROWS_DEFAULT.
+// Entry points.  lstm_fwd / lstm_bwd take 1 <= B <= 64 and run one pass of
+// 64 rows.  lstm_fwd_multi / lstm_bwd_multi take 1 <= B <= 256; `rows` is
+// their pass size P: 64 (128 workgroups, the 64-row grid) or 128 (256
+// workgroups); 0 takes R2D2_LSTM_MULTI_ROWS, default
+// LSTM_MULTI_ROWS_DEFAULT.  Each direction has ONE launch helper, which
+// both of its entry points call.
 // ---------------------------------------------------------------------------
+#define LSTM_SINGLE_MAX_B 64
 #define LSTM_MULTI_MAX_B 256
 #define LSTM_MULTI_ROWS_DEFAULT 128
 
@@ -1349,26 +782,22 @@ static int lstm_multi_rows(int64_t rows) {
     return rows ? (int)rows : rows_env;
 }
 
-static void lstm_check_ws(const torch::Tensor& ws) {
-    TORCH_CHECK(ws.defined() && ws.is_cuda() && ws.is_contiguous()
-                && ws.scalar_type() == torch::kInt32
-                && ws.numel() * 4 >= (long)sizeof(GridBar),
-                "barrier_ws must be a contiguous CUDA int32 tensor of >= ",
-                sizeof(GridBar) / 4, " words");
-}
-
-std::vector<torch::Tensor> lstm_fwd_multi(
-    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
-    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
-    torch::Tensor barrier_ws, bool want_stash, int64_t rows) {
+// `multi` says which entry point calls (`who` names it in messages); `rows`
+// is read only for the multi-pass one.
+static std::vector<torch::Tensor> lstm_fwd_launch(
+    const char* who, bool multi, int64_t rows,
+    torch::Tensor& X0, torch::Tensor& X1, torch::Tensor& Whh0,
+    torch::Tensor& Whh1, torch::Tensor& init0, torch::Tensor& init1,
+    torch::Tensor& lens, torch::Tensor& barrier_ws, bool want_stash) {
     TORCH_CHECK(X0.defined() && X0.dim() == 3, "X0 must be (B, T, 4H)");
     long B = X0.size(0), T = X0.size(1);
     long H4 = X0.size(2);
     long H = H4 / 4;
-    TORCH_CHECK(H4 == 2048, "lstm_fwd_multi is instantiated for H=512");
-    TORCH_CHECK(B >= 1 && B <= LSTM_MULTI_MAX_B,
-                "1 <= B <= 256 per multi-pass launch, got B = ", B);
-    const int P = lstm_multi_rows(rows);
+    TORCH_CHECK(H4 == 2048, who, " is instantiated for H=512");
+    const long max_b = multi ? LSTM_MULTI_MAX_B : LSTM_SINGLE_MAX_B;
+    TORCH_CHECK(B >= 1 && B <= max_b, "1 <= B <= ", max_b, " per ", who,
+                " launch, got B = ", B);
+    const int P = multi ? lstm_multi_rows(rows) : LSTM_SINGLE_MAX_B;
     bool two = X1.defined() && X1.numel() > 0;
     lstm_check(X0, "X0", torch::kBFloat16, {B, T, H4});
     lstm_check(Whh0, "Whh0", torch::kBFloat16, {H4, H});
@@ -1389,18 +818,24 @@ std::vector<torch::Tensor> lstm_fwd_multi(
     auto C1 = two ? torch::empty({B, T + 1, H}, f32) : torch::Tensor();
     auto stash = want_stash ? torch::empty({B, T, H4}, bf) : torch::Tensor();
 
-    const int ngroups = P / 32;                 // 32-row groups per pass
+    // lstm_fwd at B <= 32: the whole batch is ONE 64-row group of 8-unit
+    // slices.  Everything else: 32-row groups of 16-unit slices (the
+    // measured default: fewer/fatter workgroups, half the handoff producers
+    // per counter and half the total h re-read).
+    const bool whole = !multi && B <= 32;
+    const int ngroups = whole ? 1 : P / 32;
     const int npasses = (int)((B + P - 1) / P);
-    const int nblocks = (int)(H / 16) * ngroups * (two ? 2 : 1);
+    const int nblocks = (int)H / (whole ? 8 : 16) * ngroups * (two ? 2 : 1);
     static_assert(2 * (128 / 32) * 32 <= LSTM_MAX_FLAGS, "counter groups");
+    auto kernel = whole ? lstm_fwd_kernel<512, 64, 8>
+                        : lstm_fwd_kernel<512, 32, 16>;
     auto stream = at::cuda::getCurrentCUDAStream();
     zero_ws(barrier_ws, stream.stream());
     auto bp = [](torch::Tensor& t) {
         return t.defined()
             ? reinterpret_cast<__hip_bfloat16*>(t.data_ptr()) : nullptr;
     };
-    hipLaunchKernelGGL((lstm_fwd_multi_kernel<512, 32, 16>), dim3(nblocks),
-        dim3(256), 0, stream.stream(),
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), 0, stream.stream(),
         reinterpret_cast<const __hip_bfloat16*>(X0.data_ptr()),
         two ? reinterpret_cast<const __hip_bfloat16*>(X1.data_ptr()) : nullptr,
         reinterpret_cast<const __hip_bfloat16*>(Whh0.data_ptr()),
@@ -1420,18 +855,22 @@ std::vector<torch::Tensor> lstm_fwd_multi(
     return out;
 }
 
-torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
-                             torch::Tensor Hout, torch::Tensor dHext,
-                             torch::Tensor Whh_bwd, torch::Tensor lens,
-                             torch::Tensor barrier_ws, int64_t rows) {
+// Hout is part of the Python signature and is checked, but no kernel reads it.
+static torch::Tensor lstm_bwd_launch(
+    const char* who, bool multi, int64_t rows,
+    torch::Tensor& stash, torch::Tensor& Cout, torch::Tensor& Hout,
+    torch::Tensor& dHext, torch::Tensor& Whh_bwd, torch::Tensor& lens,
+    torch::Tensor& barrier_ws) {
     TORCH_CHECK(stash.defined() && stash.dim() == 3,
                 "stash must be (B, T, 4H)");
     long B = stash.size(0), T = stash.size(1), H4 = stash.size(2);
     long H = H4 / 4;
-    TORCH_CHECK(H4 == 2048, "lstm_bwd_multi is instantiated for H=512");
-    TORCH_CHECK(B >= 1 && B <= LSTM_MULTI_MAX_B,
-                "1 <= B <= 256 per multi-pass launch, got B = ", B);
-    const int P = lstm_multi_rows(rows);
+    TORCH_CHECK(H4 == 2048, who, " is instantiated for H=512");
+    // rows past the last pass would come back unwritten from torch::empty
+    const long max_b = multi ? LSTM_MULTI_MAX_B : LSTM_SINGLE_MAX_B;
+    TORCH_CHECK(B >= 1 && B <= max_b, "1 <= B <= ", max_b, " per ", who,
+                " launch, got B = ", B);
+    const int P = multi ? lstm_multi_rows(rows) : LSTM_SINGLE_MAX_B;
     lstm_check(stash, "stash", torch::kBFloat16, {B, T, H4});
     lstm_check(Cout, "Cout", torch::kFloat32, {B, T + 1, H});
     lstm_check(Hout, "Hout", torch::kBFloat16, {B, T + 1, H});
@@ -1440,13 +879,22 @@ torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
     lstm_check(lens, "lens", torch::kInt32, {B});
     lstm_check_ws(barrier_ws);
     auto dgates = torch::empty({B, T, H4}, stash.options());
-    const int ngroups = P / 16;                 // 16-row groups per pass
+
+    // Batch QUARTERS (16-row groups, KSPLIT 4; 128 wgs per 64 rows) are the
+    // default: measured 0.71 vs 0.95 ms against halves at 64 rows (the
+    // backward is CU-coverage bound); with B <= 32 the quarters past the
+    // batch hold no rows.  lstm_bwd at 33 <= B <= 48 runs two 32-row halves
+    // (KSPLIT 2) instead.
+    const bool halves = !multi && B > 32 && B <= 48;
+    const int ngroups = P / (halves ? 32 : 16);
     const int npasses = (int)((B + P - 1) / P);
-    const int nblocks = (int)(H / 16) * ngroups;
+    const int nblocks = (int)H / 16 * ngroups;
+    static_assert((128 / 16) * 32 <= LSTM_MAX_FLAGS, "counter groups");
+    auto kernel = halves ? lstm_bwd_kernel<512, 32, 16>
+                         : lstm_bwd_kernel<512, 16, 16>;
     auto stream = at::cuda::getCurrentCUDAStream();
     zero_ws(barrier_ws, stream.stream());
-    hipLaunchKernelGGL((lstm_bwd_multi_kernel<512, 16, 16>), dim3(nblocks),
-        dim3(256), 0, stream.stream(),
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), 0, stream.stream(),
         reinterpret_cast<const __hip_bfloat16*>(stash.data_ptr()),
         Cout.data_ptr<float>(), dHext.data_ptr<float>(),
         reinterpret_cast<const __hip_bfloat16*>(Whh_bwd.data_ptr()),
@@ -1455,4 +903,36 @@ torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
         reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),
         (int)B, (int)T, ngroups, npasses);
     return dgates;
+}
+
+std::vector<torch::Tensor> lstm_fwd(
+    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
+    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
+    torch::Tensor barrier_ws, bool want_stash) {
+    return lstm_fwd_launch("lstm_fwd", false, 0, X0, X1, Whh0, Whh1, init0,
+                           init1, lens, barrier_ws, want_stash);
+}
+
+std::vector<torch::Tensor> lstm_fwd_multi(
+    torch::Tensor X0, torch::Tensor X1, torch::Tensor Whh0, torch::Tensor Whh1,
+    torch::Tensor init0, torch::Tensor init1, torch::Tensor lens,
+    torch::Tensor barrier_ws, bool want_stash, int64_t rows) {
+    return lstm_fwd_launch("lstm_fwd_multi", true, rows, X0, X1, Whh0, Whh1,
+                           init0, init1, lens, barrier_ws, want_stash);
+}
+
+torch::Tensor lstm_bwd(torch::Tensor stash, torch::Tensor Cout,
+                       torch::Tensor Hout, torch::Tensor dHext,
+                       torch::Tensor Whh_bwd, torch::Tensor lens,
+                       torch::Tensor barrier_ws) {
+    return lstm_bwd_launch("lstm_bwd", false, 0, stash, Cout, Hout, dHext,
+                           Whh_bwd, lens, barrier_ws);
+}
+
+torch::Tensor lstm_bwd_multi(torch::Tensor stash, torch::Tensor Cout,
+                             torch::Tensor Hout, torch::Tensor dHext,
+                             torch::Tensor Whh_bwd, torch::Tensor lens,
+                             torch::Tensor barrier_ws, int64_t rows) {
+    return lstm_bwd_launch("lstm_bwd_multi", true, rows, stash, Cout, Hout,
+                           dHext, Whh_bwd, lens, barrier_ws);
 }

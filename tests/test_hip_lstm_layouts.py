@@ -7,11 +7,11 @@ The host wrappers pick a template instantiation from the batch size B:
     33 .. 48     <512, 32, 16>, 2 halves       <512, 32, 16>, KSPLIT 2, 2 halves
     49 .. 64     <512, 32, 16>, 2 halves       <512, 16, 16>, KSPLIT 4, 4 quarters
 
-(lstm_bwd picks 64 rows for B <= 32, but the line that clamps the row count
-to {8, 16, 32} turns that into 16: its <512, 64, 16> branch is never taken.
-A build whose quartered backward used the wrong rows failed these tests at
-B = 32 as well as at 49 and 64, which is how that showed.  With B <= 32 the
-quarters past the batch hold no rows.)
+(These four instantiations are all the build has; the same two templates
+also serve lstm_fwd_multi / lstm_bwd_multi, see test_hip_lstm_multi.py.
+With B <= 32 the backward's quarters past the batch hold no rows: a build
+whose quartered backward used the wrong rows failed these tests at B = 32 as
+well as at 49 and 64.)
 
 B in {1, 32, 33, 48, 49, 64} runs every column at a full last tile and at a
 one-row last tile (1: one row in all; 33: second half holds 1 row; 49:
