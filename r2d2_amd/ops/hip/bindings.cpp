@@ -85,6 +85,9 @@ torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
 torch::Tensor assemble_rin(torch::Tensor latent, torch::Tensor la,
                            torch::Tensor lr, int64_t kin_pad);
 void handoff_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks);
+void handoff_payload_bench(torch::Tensor barrier_ws, torch::Tensor scratch,
+                           int64_t steps, int64_t nblocks, int64_t kb,
+                           int64_t mode);
 void handoff_counter_bench(torch::Tensor barrier_ws, int64_t steps,
                            int64_t nblocks);
 std::vector<torch::Tensor> lstm_fwd(
@@ -246,6 +249,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("assemble_rin", &assemble_rin,
           "fused LSTM-input row assembly (latent | action | reward | pad)");
     m.def("handoff_bench", &handoff_bench, "producer-flag handoff microbench");
+    m.def("handoff_payload_bench", &handoff_payload_bench,
+          "counter handoff behind kb KB of stores per block: mode 0 plain "
+          "stores + release fence, mode 1 sc1 stores, no fence");
     m.def("handoff_counter_bench", &handoff_counter_bench,
           "counter-aggregated handoff microbench");
     m.def("dueling_combine", &dueling_combine, "q = V + A - mean(A)");

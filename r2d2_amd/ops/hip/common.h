@@ -34,6 +34,29 @@ __device__ __forceinline__ bf16x8 zero_bf16x8() {
     return r.v;
 }
 
+// ---------------------------------------------------------------------------
+// Write-through 16-byte stores for payloads handed to other workgroups inside
+// a launch (HIP guide §6 G16, recipe R1): the sc1 bit sends the line through
+// this XCD's L2, so the publish needs no release fence — every storing wave
+// drains with s_waitcnt vmcnt(0), the workgroup barriers, one lane signals.
+// The descriptor covers exactly `bytes` from `base` (a store past it is
+// dropped by the range check); build it from wave-uniform values only.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_store_rsrc(void* base,
+                                                                  long bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+}
+
+__device__ __forceinline__ void store_bf16x8_sc1(__amdgpu_buffer_rsrc_t rsrc,
+                                                 long elem_off, bf16x8 v) {
+    union { bf16x8 v; u32x4 u; } r;
+    r.v = v;
+    __builtin_amdgcn_raw_buffer_store_b128(r.u, rsrc, (int)(elem_off * 2), 0,
+                                           /*aux: sc1*/ 16);
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------

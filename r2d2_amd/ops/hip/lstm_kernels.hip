@@ -17,9 +17,14 @@
 //   lstm_bwd_multi); the 64-row entry points are its one-pass case.
 // - NO global barrier: the time index makes the h exchange naturally
 //   double-buffered, so each step is synchronized by PRODUCER FLAGS only
-//   (HIP guide §6 G16: plain h stores -> per-wave vmcnt drain ->
-//   __syncthreads -> release fence -> relaxed per-slice flag; consumers
-//   poll 64 flags lane-parallel, one acquire fence, then plain loads).
+//   (HIP guide §6 G16 recipe R1: the handed-off bytes ONLY — the h slice
+//   forward, dgates[t] backward — go out first, as 16-byte write-through
+//   (sc1) stores -> per-wave vmcnt drain -> __syncthreads -> one relaxed
+//   agent counter add, with NO release fence; c and the gate stash are
+//   read after the launch only and are stored after the publish.  The
+//   consumer polls relaxed, ONE agent acquire, that lane's vmcnt wait,
+//   __syncthreads, then plain loads).  Loads that do not depend on the
+//   recurrence (X[t]; dHext, stash, Cout) are issued BEFORE the await.
 //   Flag words are zeroed by a tiny kernel before every launch (a
 //   CAPTURED hipMemsetAsync replays a garbage fill value — see
 //   zero_gridbar_kernel); max skew
@@ -112,22 +117,24 @@ __device__ __forceinline__ bool await_slices(unsigned* flags, int nflags,
 
 // ---------------------------------------------------------------------------
 // Counter-aggregated hand-off (the production protocol): ONE atomic counter
-// per (net, batch-half) group on its own cacheline.  publish = release
-// fence + atomicAdd(1); await = poll until counter >= nprod * value.  The
+// per (net, batch-half) group on its own cacheline.  publish = drain of the
+// write-through payload stores + atomicAdd(1) (the release-fence form
+// survives in handoff_counter_bench_kernel, which prices it with nothing
+// dirty); await = poll until counter >= nprod * value.  The
 // protocol's self-limiting skew (a producer cannot be >1 step ahead of the
 // slowest in its group — it must await the whole group before advancing)
 // makes the sum threshold equivalent to per-producer flags, at ~2/3 the
 // per-step cost (tools/lstm_handoff_bench.py: 2.4 vs 3.4 us at 64 wgs).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void publish_count(unsigned* ctr) {
+    // R1 publish: the payload went out as 16-byte sc1 (write-through) stores,
+    // so there is NO release fence.  Every wave drains its own stores, the
+    // barrier collects the waves, one lane signals.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
     __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (threadIdx.x == 0)
         __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 __device__ __forceinline__ bool await_count(unsigned* ctr, unsigned target,
@@ -151,7 +158,10 @@ __device__ __forceinline__ bool await_count(unsigned* ctr, unsigned target,
                 break;
             }
         }
+        // ONE agent acquire after the match; this lane waits for the
+        // invalidate before the barrier lets the other waves load
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ok_c = ok;
     }
     __syncthreads();
@@ -248,6 +258,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
     __shared__ float s_gates[BROWS][GCOLS + 4];
     __shared__ float s_c[BROWS][UNITS];
     __shared__ __hip_bfloat16 s_hrow[BROWS][UNITS];
+    __shared__ int s_len[BROWS];
 
     // loaded ONCE for all passes
     for (int e = threadIdx.x * 8; e < GCOLS * H; e += blockDim.x * 8) {
@@ -272,37 +283,98 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
 
     constexpr int CHUNKS = (BROWS * H) / 8;
 
+    // descriptor of this net's whole Hout for the write-through h stores
+    const __amdgpu_buffer_rsrc_t hout_rsrc =
+        make_store_rsrc(Hout, (long)B * (T + 1) * H * 2);
+    // (row, gate) work that is NOT the handoff — the X loads and the stash
+    // stores — goes to the upper waves where the row group has up to 32
+    // rows: wave 0 stores the h slice and polls the counter, and a poll
+    // waits for everything its wave still has in flight.
+    const int xtid = (threadIdx.x + 128) & 255;
+
     for (int pass = 0; pass < npasses; ++pass) {
         const int b0 = pass * P + grp * BROWS;
         const int Bl = min(B - b0, BROWS);    // <= 0: empty row group
         const unsigned base_pub = (unsigned)pass * (unsigned)(T + 1);
+        // the last step's c and stash stores read s_c / s_gates after its
+        // publish: let them finish before the pass init rewrites s_c
+        if (pass > 0) __syncthreads();
+        // The handed-off payload: this wg's (Bl x UNITS) slice of h at time
+        // index tt, from s_hrow, as 16-byte write-through stores.
+        auto store_h_slice = [&](int tt) {
+            constexpr int H8 = UNITS / 8;        // 16-B pieces per h row
+            int tid = threadIdx.x;
+            if (tid < BROWS * H8) {
+                int b = tid / H8, piece = tid % H8;
+                if (b < Bl) {
+                    long off = ((long)(b0 + b) * (T + 1) + tt) * H + u0
+                               + piece * 8;
+                    store_bf16x8_sc1(hout_rsrc, off,
+                                     *reinterpret_cast<bf16x8*>(
+                                         &s_hrow[b][piece * 8]));
+                }
+            }
+        };
         // h0 -> Hout[:,0] (this wg's slice); c0 -> LDS-resident cell state
         for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
             int bl = p / UNITS, j = p % UNITS;
             int b = b0 + bl;
             int u = u0 + j;
-            Hout[((long)b * (T + 1)) * H + u] = f2bf(init[(long)b * H + u]);
+            s_hrow[bl][j] = f2bf(init[(long)b * H + u]);
             Cout[((long)b * (T + 1)) * H + u] = init[((long)B + b) * H + u];
             s_c[bl][j] = init[((long)B + b) * H + u];
         }
+        // the rows' lengths, read once per pass
+        if (threadIdx.x < BROWS)
+            s_len[threadIdx.x] =
+                ((int)threadIdx.x < Bl) ? lens[b0 + threadIdx.x] : 0;
+        __syncthreads();
+        store_h_slice(0);
         publish_count(ctr);
 
         for (int t = 0; t < T; ++t) {
+            // X[b, t] does not depend on the recurrence: issue this thread's
+            // (row, gate) loads BEFORE the await so that the cold-memory
+            // latency passes while the workgroup waits for its group
+            const int xrow = xtid / 4;
+            const int xg = xtid % 4;
+            bf16x8 xpre[UNITS / 8];
+            if (xrow < Bl) {
+#pragma unroll
+                for (int j8 = 0; j8 < UNITS; j8 += 8)
+                    xpre[j8 / 8] = load_bf16x8(
+                        X + ((long)(b0 + xrow) * T + t) * 4 * H + xg * H + u0
+                        + j8);
+            }
             if (!await_count(ctr, (unsigned)WGS * (base_pub + t + 1),
                              &bar->poison))
                 return;
             // bulk-stage this group's h_prev (Bl x H) into LDS
             {
+                // All loads first, branch-free (a row past Bl re-reads row
+                // Bl-1 and is zeroed on the way into LDS): a branch per
+                // load made each of them wait for the one before.
                 const long base = (long)t * H;
+                constexpr int NST = CHUNKS / 256;
+                static_assert(CHUNKS % 256 == 0, "staging pieces per thread");
+                bf16x8 hv[NST];
+                if (Bl > 0) {
 #pragma unroll
-                for (int e = threadIdx.x; e < CHUNKS; e += 256) {
+                    for (int i = 0; i < NST; ++i) {
+                        int e = threadIdx.x + i * 256;
+                        int row = min(e / (H / 8), Bl - 1);
+                        int k8 = (e % (H / 8)) * 8;
+                        hv[i] = load_bf16x8(Hout + ((long)(b0 + row) * (T + 1))
+                                            * H + base + k8);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < NST; ++i) {
+                    int e = threadIdx.x + i * 256;
                     int row = e / (H / 8);
                     int k8 = (e % (H / 8)) * 8;
-                    bf16x8 v = (row < Bl)
-                        ? load_bf16x8(Hout + ((long)(b0 + row) * (T + 1))
-                                      * H + base + k8)
-                        : zero_bf16x8();
-                    lstore8(&s_h[row][k8], v);
+                    lstore8(&s_h[row][k8],
+                            (row < Bl) ? hv[i] : zero_bf16x8());
                 }
             }
             __syncthreads();
@@ -332,25 +404,18 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
             }
             __syncthreads();
             // + X[t] (vectorized), then nonlinearities + state advance
-            {
-                int row = threadIdx.x / 4;
-                int g = threadIdx.x % 4;
-                if (row < Bl) {
+            if (xrow < Bl) {
 #pragma unroll
-                    for (int j8 = 0; j8 < UNITS; j8 += 8) {
-                        bf16x8 x8 = load_bf16x8(
-                            X + ((long)(b0 + row) * T + t) * 4 * H + g * H + u0
-                            + j8);
+                for (int j8 = 0; j8 < UNITS; j8 += 8)
 #pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            s_gates[row][g * UNITS + j8 + j] += (float)x8[j];
-                    }
-                }
+                    for (int j = 0; j < 8; ++j)
+                        s_gates[xrow][xg * UNITS + j8 + j] +=
+                            (float)xpre[j8 / 8][j];
             }
             __syncthreads();
             for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
                 int b = p / UNITS, j = p % UNITS;
-                bool active = t < lens[b0 + b];
+                bool active = t < s_len[b];
                 float i_ = 0.f, f_ = 0.f, g_ = 0.f, o_ = 0.f;
                 float c = s_c[b][j], h;
                 if (active) {
@@ -371,19 +436,15 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
                 s_gates[b][3 * UNITS + j] = o_;
             }
             __syncthreads();
-            // vectorized writers: h slice, c, gate stash
+            // Only the h slice is handed off: publish it FIRST (write-through
+            // stores, drain, barrier, counter add; no release fence).  c and
+            // the gate stash are read after the launch only, so their plain
+            // stores follow the publish, off the serial chain.
+            store_h_slice(t + 1);
+            publish_count(ctr);
             {
                 int tid = threadIdx.x;
-                constexpr int H8 = UNITS / 8;    // 16-B pieces per h row
-                if (tid < 64 * H8) {
-                    int b = tid / H8, piece = tid % H8;
-                    if (b < Bl) {
-                        long off = ((long)(b0 + b) * (T + 1) + t + 1) * H + u0
-                                   + piece * 8;
-                        lstore8(Hout + off, *reinterpret_cast<bf16x8*>(
-                            &s_hrow[b][piece * 8]));
-                    }
-                } else if (tid >= 128) {
+                if (tid >= 128) {
                     // c writers: threads [128, 256) cover BROWS rows x C4
                     // float4 pieces (BROWS*C4 <= 128 for both layouts)
                     int t2 = tid - 128;
@@ -399,8 +460,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
                 }
             }
             if (stash) {
-                int row = threadIdx.x / 4;
-                int g = threadIdx.x % 4;
+                int row = xtid / 4;
+                int g = xtid % 4;
                 if (row < Bl) {
 #pragma unroll
                     for (int j8 = 0; j8 < UNITS; j8 += 8) {
@@ -413,7 +474,6 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_kernel(
                     }
                 }
             }
-            publish_count(ctr);
         }
     }
 }
@@ -439,6 +499,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                   "one 16-col MFMA tile; 4 waves = BROWS/16 row tiles x KSPLIT");
     constexpr int WGS = H / UNITS;
     constexpr int KSPLIT = 64 / BROWS;
+    constexpr int NEL = BROWS * UNITS / 256;   // (row, unit) elements per thread
     const int grp = blockIdx.x / WGS;
     const int wid = blockIdx.x % WGS;
     const int u0 = wid * UNITS;
@@ -469,6 +530,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
     const int c0 = wk * (NCHUNK / KSPLIT);
     const int cN = c0 + NCHUNK / KSPLIT;
 
+    // descriptor of the whole dgates for the write-through stores
+    const __amdgpu_buffer_rsrc_t dg_rsrc =
+        make_store_rsrc(dgates, (long)B * T * 4 * H * 2);
+
     for (int pass = 0; pass < npasses; ++pass) {
         const int b0 = pass * P + grp * BROWS;
         const int Bl = min(B - b0, BROWS);     // <= 0: empty row group
@@ -477,9 +542,43 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
             s_dh[p / UNITS][p % UNITS] = 0.f;
             s_dc[p / UNITS][p % UNITS] = 0.f;
         }
+        // this thread's (row, unit) elements keep their rows for the whole
+        // pass: the rows' lengths are read once
+        int len_r[NEL];
+#pragma unroll
+        for (int e = 0; e < NEL; ++e) {
+            int p = threadIdx.x + e * 256;
+            len_r[e] = (p < Bl * UNITS) ? lens[b0 + p / UNITS] : 0;
+        }
         publish_count(ctr);
 
         for (int t = T - 1; t >= 0; --t) {
+            // Everything the pointwise step reads from global is a product
+            // of the forward or of the heads, none of it written in this
+            // launch: issue the loads BEFORE the await, so that they land
+            // while the workgroup waits for its group.  Rows past Bl are
+            // not read, nor is the stash at t + 1 = T.
+            struct {
+                float ext, c_next, c_prev;
+                __hip_bfloat16 i, f, g, o, f_next;
+            } pre[NEL];
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) {
+                int p = threadIdx.x + e * 256;
+                if (p >= Bl * UNITS) break;
+                int bg = b0 + p / UNITS;
+                int u = u0 + p % UNITS;
+                long so = ((long)bg * T + t) * 4 * H + u;
+                long co = ((long)bg * (T + 1) + t) * H + u;
+                pre[e].ext = dHext[((long)bg * T + t) * H + u];
+                pre[e].i = stash[so];
+                pre[e].f = stash[so + H];
+                pre[e].g = stash[so + 2 * H];
+                pre[e].o = stash[so + 3 * H];
+                pre[e].c_prev = Cout[co];
+                pre[e].c_next = Cout[co + H];
+                if (t + 1 < T) pre[e].f_next = stash[so + 4 * H + H];
+            }
             unsigned need = (unsigned)(T - t);  // pieces published for t+1
             if (!await_count(ctr, (unsigned)WGS * (base_pub + need),
                              &bar->poison))
@@ -531,14 +630,15 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                     s_rec[wk][wrow0 + crow + r][ccol] = acc[r];
             }
             __syncthreads();
-            for (int p = threadIdx.x; p < Bl * UNITS; p += blockDim.x) {
+#pragma unroll
+            for (int e = 0; e < NEL; ++e) {
+                int p = threadIdx.x + e * 256;
+                if (p >= Bl * UNITS) break;
                 int b = p / UNITS, jl = p % UNITS;
-                int bg = b0 + b;
-                int u = u0 + jl;
                 float dh, dc_in;
                 bool last = (t == T - 1);
-                bool active_next = !last && ((t + 1) < lens[bg]);
-                float ext = dHext[((long)bg * T + t) * H + u];
+                bool active_next = !last && ((t + 1) < len_r[e]);
+                float ext = pre[e].ext;
                 float rec = s_rec[0][b][jl];
 #pragma unroll
                 for (int kk = 1; kk < KSPLIT; ++kk) rec += s_rec[kk][b][jl];
@@ -546,24 +646,22 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                     dh = ext;
                     dc_in = 0.f;
                 } else if (active_next) {
-                    long so1 = ((long)bg * T + t + 1) * 4 * H + u;
-                    float f_next = bf2f(stash[so1 + H]);
+                    float f_next = bf2f(pre[e].f_next);
                     dh = ext + rec;
                     dc_in = s_dc[b][jl] * f_next;
                 } else {
                     dh = ext + s_dh[b][jl];
                     dc_in = s_dc[b][jl];
                 }
-                bool active = t < lens[bg];
-                long so = ((long)bg * T + t) * 4 * H + u;
+                bool active = t < len_r[e];
                 float di = 0.f, df = 0.f, dg = 0.f, do_ = 0.f;
                 if (active) {
-                    float i_ = bf2f(stash[so]);
-                    float f_ = bf2f(stash[so + H]);
-                    float g_ = bf2f(stash[so + 2 * H]);
-                    float o_ = bf2f(stash[so + 3 * H]);
-                    float tc = tanhf(Cout[((long)bg * (T + 1) + t + 1) * H + u]);
-                    float c_prev = Cout[((long)bg * (T + 1) + t) * H + u];
+                    float i_ = bf2f(pre[e].i);
+                    float f_ = bf2f(pre[e].f);
+                    float g_ = bf2f(pre[e].g);
+                    float o_ = bf2f(pre[e].o);
+                    float tc = tanhf(pre[e].c_next);
+                    float c_prev = pre[e].c_prev;
                     float dc = dc_in + dh * o_ * (1.f - tc * tc);
                     di = dc * g_ * i_ * (1.f - i_);
                     df = dc * c_prev * f_ * (1.f - f_);
@@ -581,7 +679,9 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                 *(__bf16*)&s_dgout[b][3 * UNITS + jl] = (__bf16)do_;
             }
             __syncthreads();
-            // vectorized dgates writes: thread (b, g) -> UNITS/8 x 16 B
+            // dgates[t] is the whole handed-off payload: thread (b, g) ->
+            // UNITS/8 x 16 B write-through stores, then drain, barrier and
+            // counter add (no release fence)
             {
                 int tid = threadIdx.x;
                 int b = tid / 4;
@@ -591,9 +691,9 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_kernel(
                     for (int rep = 0; rep < UNITS / 8; ++rep) {
                         long off = ((long)(b0 + b) * T + t) * 4 * H + g * H + u0
                                    + rep * 8;
-                        lstore8(dgates + off,
-                                *reinterpret_cast<bf16x8*>(
-                                    &s_dgout[b][g * UNITS + rep * 8]));
+                        store_bf16x8_sc1(dg_rsrc, off,
+                                         *reinterpret_cast<bf16x8*>(
+                                             &s_dgout[b][g * UNITS + rep * 8]));
                     }
                 }
             }
@@ -626,6 +726,61 @@ __global__ void handoff_counter_bench_kernel(GridBar* bar, int steps,
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
         __syncthreads();
+    }
+}
+
+// The counter handoff under the kernels' real conditions.  Before every
+// publish each block stores `kb` KB of its own scratch region, 16 B per lane:
+//   mode 0  plain stores, then the release-fence publish (what the LSTM paid
+//           while Cout / stash were stored in front of the fence)
+//   mode 1  write-through (sc1) stores, drain, barrier, counter add, NO
+//           release fence (the publish the LSTM kernels use now)
+// scratch holds nblocks * kb KB; block b writes only [b * kb KB, (b+1) * kb KB).
+__global__ void handoff_payload_bench_kernel(GridBar* bar,
+                                             __hip_bfloat16* scratch,
+                                             long scratch_bytes, int steps,
+                                             int nblocks, int kb, int mode) {
+    unsigned* ctr = &bar->flags[0];
+    const __amdgpu_buffer_rsrc_t rsrc = make_store_rsrc(scratch, scratch_bytes);
+    const long base = (long)blockIdx.x * kb * 512;     // bf16 elements
+    const int pieces = kb * 64;                        // 16-B pieces per block
+    __shared__ int dead;
+    if (threadIdx.x == 0) dead = 0;
+    __syncthreads();
+    for (int t = 0; t < steps; ++t) {
+        bf16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (__bf16)(float)(t + j);
+        for (int p = threadIdx.x; p < pieces; p += blockDim.x) {
+            if (mode == 1) store_bf16x8_sc1(rsrc, base + (long)p * 8, v);
+            else lstore8(scratch + base + (long)p * 8, v);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (mode == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            long spins = 0;
+            while (__hip_atomic_load(ctr, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT)
+                   < (unsigned)(nblocks * (t + 1))) {
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > (long)2e8) {
+                    __hip_atomic_store(&bar->poison, 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                    dead = 1;
+                    break;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+        if (dead) return;          // uniform: every thread reads the LDS flag
     }
 }
 
@@ -726,6 +881,27 @@ void handoff_counter_bench(torch::Tensor barrier_ws, int64_t steps,
                        (int)steps, (int)nblocks);
 }
 
+void handoff_payload_bench(torch::Tensor barrier_ws, torch::Tensor scratch,
+                           int64_t steps, int64_t nblocks, int64_t kb,
+                           int64_t mode) {
+    TORCH_CHECK(scratch.is_cuda() && scratch.is_contiguous()
+                && scratch.scalar_type() == torch::kBFloat16,
+                "scratch must be a contiguous CUDA bf16 tensor");
+    TORCH_CHECK(nblocks >= 1 && nblocks <= 256 && kb >= 0 && kb <= 64
+                && steps >= 1 && (mode == 0 || mode == 1),
+                "1 <= nblocks <= 256, 0 <= kb <= 64, mode 0 or 1");
+    const long bytes = scratch.numel() * 2;
+    TORCH_CHECK(bytes >= nblocks * kb * 1024 && bytes < (1L << 31),
+                "scratch must hold nblocks * kb KB");
+    auto stream = at::cuda::getCurrentCUDAStream();
+    zero_ws(barrier_ws, stream.stream());
+    hipLaunchKernelGGL(handoff_payload_bench_kernel, dim3((int)nblocks),
+                       dim3(256), 0, stream.stream(),
+                       reinterpret_cast<GridBar*>(barrier_ws.data_ptr()),
+                       reinterpret_cast<__hip_bfloat16*>(scratch.data_ptr()),
+                       bytes, (int)steps, (int)nblocks, (int)kb, (int)mode);
+}
+
 void handoff_bench(torch::Tensor barrier_ws, int64_t steps, int64_t nblocks) {
     auto stream = at::cuda::getCurrentCUDAStream();
     zero_ws(barrier_ws, stream.stream());
@@ -809,6 +985,9 @@ static std::vector<torch::Tensor> lstm_fwd_launch(
         lstm_check(init1, "init1", torch::kFloat32, {2, B, H});
     }
     lstm_check_ws(barrier_ws);
+    // the write-through h stores address Hout through a buffer descriptor
+    TORCH_CHECK(B * (T + 1) * H * 2 < (1L << 31), who,
+                ": Hout of 2 GiB or more (B * T too large)");
 
     auto bf = X0.options();
     auto f32 = X0.options().dtype(torch::kFloat32);
@@ -878,6 +1057,9 @@ static torch::Tensor lstm_bwd_launch(
     lstm_check(Whh_bwd, "Whh_bwd", torch::kBFloat16, {H, H4});
     lstm_check(lens, "lens", torch::kInt32, {B});
     lstm_check_ws(barrier_ws);
+    // the write-through dgates stores address it through a buffer descriptor
+    TORCH_CHECK(B * T * H4 * 2 < (1L << 31), who,
+                ": dgates of 2 GiB or more (B * T too large)");
     auto dgates = torch::empty({B, T, H4}, stash.options());
 
     // Batch QUARTERS (16-row groups, KSPLIT 4; 128 wgs per 64 rows) are the
