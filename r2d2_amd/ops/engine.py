@@ -450,14 +450,24 @@ class HipNetworkEngine:
                                           xp=getattr(self, "_xp", None))
         M = obs_hwc_u8.shape[0]
         if self._fwd_band:
-            # per-image band forwards: image + weights LDS-resident, one
-            # global read/dequant per input element
+            # per-image band forward: image LDS-resident, one global
+            # read/dequant per input element
             a1 = m.conv_fwd_band(obs_hwc_u8, pack.w1t, pack.b1, 1, M)
-            a2 = m.conv_fwd_band(a1, pack.w2t, pack.b2, 2, M)
-            a3 = m.conv_fwd_band(a2, pack.w3t, pack.b3, 3, M)
         else:
             a1 = m.conv_fwd(obs_hwc_u8, pack.w1t, pack.b1, 1, M, 84, 84,
                             20, 20, True)
+        return self._encoder_from_a1(pack, a1)
+
+    def _encoder_from_a1(self, pack, a1):
+        """Nature encoder above conv1: a1 (M*400, 32) bf16 -> latent (M, 512)
+        bf16 + stashes.  conv1 runs once for the online and the target
+        network in the train step (conv1_fwd_dual), so it is not in here."""
+        m = self.m
+        M = a1.shape[0] // 400
+        if self._fwd_band:
+            a2 = m.conv_fwd_band(a1, pack.w2t, pack.b2, 2, M)
+            a3 = m.conv_fwd_band(a2, pack.w3t, pack.b3, 3, M)
+        else:
             a2 = m.conv_fwd(a1, pack.w2t, pack.b2, 2, M, 20, 20, 9, 9, True)
             a3 = m.conv_fwd(a2, pack.w3t, pack.b3, 3, M, 9, 9, 7, 7, True)
         flat = a3.view(M, 3136)
@@ -656,10 +666,23 @@ class HipNetworkEngine:
         if self.impala:
             # pack frames once; online and target share the padded u8 tensor
             self._xp = impala_ops.pack_obs(m, self.online.imp, obs_hwc)
-        lat_o, enc_stash = self._encoder_fwd(self.online, obs_hwc)
-        self._mark("enc_online")
-        lat_t, _ = self._encoder_fwd(self.target, obs_hwc, want_stash=False)
-        self._mark("enc_target")
+        if self._fwd_band and not (self.mlp or self.impala):
+            # both networks' conv1 from one staging of each frame
+            a1_o, a1_t = m.conv1_fwd_dual(
+                obs_hwc, self.online.w1t, self.online.b1, self.target.w1t,
+                self.target.b1, B * T)
+            self._mark("conv1_dual")
+            lat_o, enc_stash = self._encoder_from_a1(self.online, a1_o)
+            self._mark("enc_online")
+            lat_t, _ = self._encoder_from_a1(self.target, a1_t)
+            del a1_t                    # dead after the target's conv2
+            self._mark("enc_target")
+        else:
+            lat_o, enc_stash = self._encoder_fwd(self.online, obs_hwc)
+            self._mark("enc_online")
+            lat_t, _ = self._encoder_fwd(self.target, obs_hwc,
+                                         want_stash=False)
+            self._mark("enc_target")
         rin_o, X_o = self._lstm_input(self.online, lat_o, la, lr)
         _, X_t = self._lstm_input(self.target, lat_t, la, lr)
         self._mark("lstm_input")

@@ -77,6 +77,11 @@ std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
 torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
                             torch::Tensor bias, int64_t conv_id, int64_t N,
                             int64_t max_wgs);
+std::vector<torch::Tensor> conv1_fwd_dual(torch::Tensor in, torch::Tensor Wt0,
+                                          torch::Tensor bias0,
+                                          torch::Tensor Wt1,
+                                          torch::Tensor bias1, int64_t N,
+                                          int64_t max_wgs);
 torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
                               torch::Tensor actx, int64_t conv_id, int64_t N,
                               int64_t max_wgs);
@@ -225,6 +230,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "conv1, in registers for the 64-output layers)",
           py::arg("in"), py::arg("Wt"), py::arg("bias"), py::arg("conv_id"),
           py::arg("N"), py::arg("max_wgs") = 0);
+    m.def("conv1_fwd_dual", &conv1_fwd_dual,
+          "conv1 of two networks from one LDS staging of each frame (both "
+          "weight sets in registers, 16-byte stores); returns (out0, out1)",
+          py::arg("in"), py::arg("Wt0"), py::arg("bias0"), py::arg("Wt1"),
+          py::arg("bias1"), py::arg("N"), py::arg("max_wgs") = 0);
     m.def("conv_dgrad_band", &conv_dgrad_band,
           "per-image band dgrad: dY staged once in LDS in a zero halo, all "
           "parity classes in one launch, dX stored through LDS with the "

@@ -880,6 +880,159 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_band64_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// conv1_fwd_dual: conv1 of TWO networks (online and target) from one staging
+// of each frame.  The networks differ only in a (32, K) weight matrix and a
+// bias, so the u8 read, the dequant and the LDS image are shared and only
+// the MFMAs and the stores double.
+//   W    both networks' weights in registers (load_b_regs, 2 x K/32 x 2
+//        fragments: 128 VGPRs at four channels, 32 at one); no LDS slab.
+//        Every wave holds both networks and the waves split the image's 25
+//        row fragments 7/6/6/6, so an A fragment is read from LDS once and
+//        feeds four MFMAs.  The k order per output element is
+//        conv_fwd_band_kernel's: outputs are bit-equal to it.
+//   in   the next image's u8 bytes are loaded into registers (8 bytes per
+//        lane and load, the alignment the frames really have) before the
+//        MFMA loop and dequantised into the LDS image after the barrier that
+//        ends it; two barriers per image.
+//   out  a wave's 32 x 32 tile (bias + ReLU applied) goes through a private
+//        LDS scratch and leaves as 16-byte stores contiguous over the wave:
+//        an output row is 64 B, a 16-row fragment one 1 KB run.  The scratch
+//        row stride of 80 B spreads the four rows a 2-byte write instruction
+//        touches over disjoint banks.
+// ---------------------------------------------------------------------------
+template <class G>
+struct Conv1Dual {
+    static constexpr int CHUNKS = G::IMG / 8;             // 8-byte u8 chunks
+    static constexpr int NPRE = (CHUNKS + 255) / 256;     // per thread
+    static constexpr int NFRAG = G::NPIX / 16;            // 25 row fragments
+    static constexpr int PER_WAVE = NFRAG / 4;            // wave 0: one more
+    static constexpr int SCR_LD = G::COUT + 8;            // 80 B rows
+    static constexpr int SCR = 32 * SCR_LD;               // per wave
+    // LDS offset of k-step ks = ks * KS_STEP + a per-lane constant
+    static constexpr int KS_STEP = 32 / G::KWC * G::INW * G::CIN;
+    static_assert(G::NPIX % 16 == 0 && NFRAG % 4 == 1 && PER_WAVE % 2 == 0,
+                  "whole fragments: pairs per wave, wave 0 one single more");
+    static_assert(G::COUT == 32 && G::IN_U8 && 32 % G::KWC == 0);
+    static_assert((G::IMG + 4 * SCR) * 2 <= 80 * 1024);
+};
+
+template <class G>
+__global__ __launch_bounds__(256, 2) void conv1_fwd_dual_kernel(
+    const unsigned char* __restrict__ in,    // (N, INH, INW, CIN) u8
+    const __hip_bfloat16* __restrict__ Wt0,  // (COUT, K) network 0
+    const float* __restrict__ bias0,
+    const __hip_bfloat16* __restrict__ Wt1,  // (COUT, K) network 1
+    const float* __restrict__ bias1,
+    __hip_bfloat16* __restrict__ out0,       // (N*NPIX, COUT)
+    __hip_bfloat16* __restrict__ out1,
+    int N, int imgs_per_wg) {
+    using D = Conv1Dual<G>;
+    constexpr int NPIX = G::NPIX, COUT = G::COUT, KSTEPS = G::K / 32;
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_img[G::IMG];
+    __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_scr[4 * D::SCR];
+
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int frow = lane & 15, kseg = (lane >> 4) * 8;
+    __hip_bfloat16* scr = s_scr + wave * D::SCR;
+
+    bf16x8 b[2][KSTEPS][2];
+    load_b_regs<KSTEPS>(b[0], Wt0, 0, lane);
+    load_b_regs<KSTEPS>(b[1], Wt1, 0, lane);
+    float bias_c[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        bias_c[0][j] = bias0[j * 16 + frow];
+        bias_c[1][j] = bias1[j * 16 + frow];
+    }
+    // this lane's k segment inside the patch: kernel row, then its run
+    const int klane = kseg / G::KWC * G::INW * G::CIN + kseg % G::KWC;
+
+    auto load_image = [&](uint2 (&pre)[D::NPRE], long n) {
+        const uint2* g = reinterpret_cast<const uint2*>(in + n * G::IMG);
+#pragma unroll
+        for (int c = 0; c < D::NPRE; ++c) {
+            int e8 = threadIdx.x + c * 256;
+            if (e8 < D::CHUNKS) pre[c] = g[e8];
+        }
+    };
+
+    // row fragments f0 .. f0 + NI - 1 of image n, both networks
+    auto tile = [&](auto ni, int f0, long n) {
+        constexpr int NI = decltype(ni)::value;
+        int pbase[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            int pp = (f0 + i) * 16 + frow;
+            pbase[i] = (pp / G::OW * G::INW + pp % G::OW) * G::S * G::CIN
+                       + klane;
+        }
+        f32x4 acc[2][NI][2] = {};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+            bf16x8 a[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                a[i] = lds_patch_row<G::CIN>(
+                    &s_img[pbase[i] + ks * D::KS_STEP]);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int i = 0; i < NI; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[q][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            a[i], b[q][ks][j], acc[q][i][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            for_each_acc(acc[q], lane, [&](int r, int c, float v) {
+                v += bias_c[q][c / 16];
+                scr[r * D::SCR_LD + c] = f2bf(fmaxf(v, 0.f));
+            });
+            // the scratch is this wave's own: order its writes before the
+            // other lanes' reads, and those before the next tile's writes
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __hip_bfloat16* go =
+                (q ? out1 : out0) + (n * NPIX + f0 * 16) * COUT + lane * 8;
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                *reinterpret_cast<bf16x8*>(go + i * 16 * COUT) =
+                    *reinterpret_cast<const bf16x8*>(
+                        &scr[(i * 16 + lane / 4) * D::SCR_LD + lane % 4 * 8]);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    };
+
+    const long n0 = (long)blockIdx.x * imgs_per_wg;
+    const long n1 = min((long)N, n0 + imgs_per_wg);
+    if (n0 >= n1) return;
+    const int f0 = wave == 0 ? 0 : 1 + wave * D::PER_WAVE;
+    uint2 pre[D::NPRE];
+    load_image(pre, n0);
+    for (long n = n0; n < n1; ++n) {
+        __syncthreads();    // every read of the previous image is done
+#pragma unroll
+        for (int c = 0; c < D::NPRE; ++c) {
+            int e8 = threadIdx.x + c * 256;
+            if (e8 < D::CHUNKS)
+                *reinterpret_cast<bf16x8*>(&s_img[e8 * 8]) =
+                    dequant8(pre[c].x, pre[c].y);
+        }
+        __syncthreads();
+        if (n + 1 < n1) load_image(pre, n + 1);
+
+        for (int t = 0; t < D::PER_WAVE; t += 2)
+            tile(std::integral_constant<int, 2>{}, f0 + t, n);
+        if (wave == 0)
+            tile(std::integral_constant<int, 1>{}, D::PER_WAVE, n);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // conv_dgrad_band: per-image dgrad, one launch per layer.  Same sums as
 // conv_dgrad_dense_kernel — k runs tap-major, co-minor, 32 per MFMA step, in
 // the parity class's tap order, out-of-image taps issued as zero fragments —
@@ -1281,6 +1434,61 @@ torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
         }
     });
     return out;
+}
+
+// conv1 of two networks on the same frames (see conv1_fwd_dual_kernel):
+// returns {out0, out1}, each bit-equal to conv_fwd_band with that network's
+// weights.  Default grids, measured at 5440 images: see docs/KERNELS.md.
+constexpr int DUAL_WGS_4CH = 512, DUAL_WGS_1CH = 2048;
+
+std::vector<torch::Tensor> conv1_fwd_dual(torch::Tensor in, torch::Tensor Wt0,
+                                          torch::Tensor bias0,
+                                          torch::Tensor Wt1,
+                                          torch::Tensor bias1, int64_t N,
+                                          int64_t max_wgs) {
+    const char* who = "conv1_fwd_dual";
+    torch::Tensor out0, out1;
+    TORCH_CHECK(N > 0 && max_wgs >= 0, who, ": N must be positive and max_wgs "
+                "non-negative");
+    // the frames are loaded 8 bytes per lane for both channel counts
+    int cin1 = conv1_cin(1, in, N, 8, 8, who);
+    dispatch_layer(1, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        if constexpr (G::IN_U8) {
+            for (const torch::Tensor* w : {&Wt0, &Wt1}) {
+                TORCH_CHECK(w->is_cuda() && w->dtype() == torch::kBFloat16
+                            && w->is_contiguous()
+                            && reinterpret_cast<uintptr_t>(w->data_ptr()) % 16
+                                   == 0, who, ": weights must be contiguous, "
+                            "16-byte aligned bf16 device tensors");
+                check_weights<G>(*w, who);
+            }
+            for (const torch::Tensor* b : {&bias0, &bias1})
+                TORCH_CHECK(b->is_cuda() && b->dtype() == torch::kFloat32
+                            && b->is_contiguous() && b->numel() == G::COUT,
+                            who, ": each bias must be ", G::COUT,
+                            " contiguous f32 on the device");
+            auto opts = in.options().dtype(torch::kBFloat16);
+            out0 = torch::empty({N * G::NPIX, G::COUT}, opts);
+            out1 = torch::empty({N * G::NPIX, G::COUT}, opts);
+            int imgs, grid;
+            band_grid(N, max_wgs > 0 ? max_wgs
+                         : (G::CIN == 1 ? DUAL_WGS_1CH : DUAL_WGS_4CH),
+                      imgs, grid);
+            hipLaunchKernelGGL(
+                (conv1_fwd_dual_kernel<G>), dim3(grid), dim3(256), 0,
+                at::cuda::getCurrentCUDAStream().stream(),
+                reinterpret_cast<const unsigned char*>(in.data_ptr()),
+                reinterpret_cast<const __hip_bfloat16*>(Wt0.data_ptr()),
+                bias0.data_ptr<float>(),
+                reinterpret_cast<const __hip_bfloat16*>(Wt1.data_ptr()),
+                bias1.data_ptr<float>(),
+                reinterpret_cast<__hip_bfloat16*>(out0.data_ptr()),
+                reinterpret_cast<__hip_bfloat16*>(out1.data_ptr()), (int)N,
+                imgs);
+        }
+    });
+    return {out0, out1};
 }
 
 // per-image band dgrad (see conv_dgrad_band_kernel).  dY is the dense,
