@@ -436,6 +436,42 @@ class HipNetworkEngine:
 
     # ------------------------------------------------------------------
     _fwd_band = os.environ.get("R2D2_CONV_FWD_BAND", "1") != "0"
+    # conv wgrads flush per-workgroup partial sums with plain stores and one
+    # reducer per layer writes .grad; 0 keeps the atomic flush + copies
+    _wgrad_slab = os.environ.get("R2D2_CONV_WGRAD_SLAB", "1") != "0"
+    _wgrad_ws = None
+
+    def _conv_bwd_slab(self, enc, ON, dflat3, a1, a2, obs_hwc, M):
+        """Nature-CNN conv backward on the slab path.  Every dY is already
+        masked (by the FC dgrad's and the conv dgrads' stores), so the wgrads
+        get no mask to re-read; each reducer overwrites its .grad views of
+        the flat buffer in torch layout, so nothing is zeroed or copied."""
+        m = self.m
+        band1 = self.C == 4
+        need = max(m.conv_wgrad_ws_floats(3, 0, M, True),
+                   m.conv_wgrad_ws_floats(2, 0, M, True),
+                   m.conv_wgrad_ws_floats(1, self.C, M, band1))
+        if self._wgrad_ws is None or self._wgrad_ws.numel() < need:
+            # one partial-sum workspace for the three layers (they run one
+            # after the other), kept from step to step
+            self._wgrad_ws = torch.empty(need, dtype=torch.float32,
+                                         device=self.device)
+        ws, no_mask = self._wgrad_ws, self._empty
+        m.conv_wgrad_band_into(dflat3, no_mask, a2, 3, M, ws,
+                               enc.conv3.weight.grad, enc.conv3.bias.grad)
+        d_a2 = m.conv_dgrad_band(dflat3, ON.w3d, a2, 3, M)
+        d_a2f = d_a2.view(M * 81, 64)
+        m.conv_wgrad_band_into(d_a2f, no_mask, a1, 2, M, ws,
+                               enc.conv2.weight.grad, enc.conv2.bias.grad)
+        d_a1 = m.conv_dgrad_band(d_a2f, ON.w2d, a1, 2, M).view(M * 400, 32)
+        # conv1: band with four channels, chunked with one (see below)
+        if band1:
+            m.conv_wgrad_band_into(d_a1, no_mask, obs_hwc, 1, M, ws,
+                                   enc.conv1.weight.grad, enc.conv1.bias.grad)
+        else:
+            m.conv_wgrad_into(d_a1, no_mask, obs_hwc, 1, M, 84, 84, 20, 20,
+                              32, 8 * 8 * self.C, ws, enc.conv1.weight.grad,
+                              enc.conv1.bias.grad)
 
     def _encoder_fwd(self, pack, obs_hwc_u8, want_stash=True):
         """obs: (M, 84, 84, C) uint8 -> latent (M, 512) bf16 + stashes.
@@ -816,6 +852,18 @@ class HipNetworkEngine:
         # are permuted into .grad afterwards (tiny tensors).
         self._mark("fc_bwd")
         dflat3 = dflat.view(M * 49, 64)   # pre-masked by a3
+        enc = net.encoder
+        if self._wgrad_slab:
+            self._conv_bwd_slab(enc, ON, dflat3, a1, a2, obs_hwc, M)
+            self._mark("conv_bwd")
+            enc.fc.weight.grad.copy_(
+                dWf.view(512, 7, 7, 64).permute(0, 3, 1, 2).reshape(512, 3136))
+            enc.fc.bias.grad.copy_(dbf)
+            if grad_hook is not None:
+                grad_hook("encoder")
+            self._mark("grad_write")
+            return loss.squeeze(0), prio
+        # R2D2_CONV_WGRAD_SLAB=0: the atomic-flush wgrads (A/B reference)
         # per-image band wgrads: whole input image staged in LDS once
         # (single dequant per element; conv1 patch traffic 557 -> 154 MB)
         dW3, db3 = m.conv_wgrad_band(dflat3, a3, a2, 3, M)
@@ -843,8 +891,6 @@ class HipNetworkEngine:
             dW1, db1 = m.conv_wgrad(d_a1.view(M * 400, 32), a1, obs_hwc, 1,
                                     M, 84, 84, 20, 20, 32, 8 * 8 * self.C)
         self._mark("conv_bwd")
-
-        enc = net.encoder
 
         def conv_grad(dwt, cout, kh, kw, cin):
             return dwt.view(cout, kh, kw, cin).permute(0, 3, 1, 2)

@@ -71,9 +71,19 @@ std::vector<torch::Tensor> conv_wgrad(torch::Tensor dY, torch::Tensor act,
                                       int64_t N, int64_t INH, int64_t INW,
                                       int64_t OH, int64_t OW, int64_t COUT,
                                       int64_t K);
+void conv_wgrad_into(torch::Tensor dY, torch::Tensor act, torch::Tensor in,
+                     int64_t conv_id, int64_t N, int64_t INH, int64_t INW,
+                     int64_t OH, int64_t OW, int64_t COUT, int64_t K,
+                     torch::Tensor ws, torch::Tensor dW, torch::Tensor db);
 std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
                                            torch::Tensor in, int64_t conv_id,
-                                           int64_t N);
+                                           int64_t N, int64_t max_wgs);
+void conv_wgrad_band_into(torch::Tensor dY, torch::Tensor act,
+                          torch::Tensor in, int64_t conv_id, int64_t N,
+                          torch::Tensor ws, torch::Tensor dW, torch::Tensor db,
+                          int64_t max_wgs);
+int64_t conv_wgrad_ws_floats(int64_t conv_id, int64_t cin1, int64_t N,
+                             bool band);
 torch::Tensor conv_fwd_band(torch::Tensor in, torch::Tensor Wt,
                             torch::Tensor bias, int64_t conv_id, int64_t N,
                             int64_t max_wgs);
@@ -224,7 +234,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_wgrad", &conv_wgrad, "MFMA conv backward-weight");
     m.def("conv_wgrad_band", &conv_wgrad_band,
           "per-image band wgrad (whole input image LDS-staged, one dequant "
-          "per element, register accumulation, one atomic flush per wg)");
+          "per element, register accumulation, one atomic flush per wg); an "
+          "empty act = dY is pre-masked",
+          py::arg("dY"), py::arg("act"), py::arg("in"), py::arg("conv_id"),
+          py::arg("N"), py::arg("max_wgs") = 0);
+    m.def("conv_wgrad_band_into", &conv_wgrad_band_into,
+          "band wgrad without atomics: per-workgroup partial sums stored to "
+          "the workspace ws, then one reducer overwrites dW (torch layout) "
+          "and db; bitwise reproducible",
+          py::arg("dY"), py::arg("act"), py::arg("in"), py::arg("conv_id"),
+          py::arg("N"), py::arg("ws"), py::arg("dW"), py::arg("db"),
+          py::arg("max_wgs") = 0);
+    m.def("conv_wgrad_into", &conv_wgrad_into,
+          "chunked wgrad with the slab flush and reducer of "
+          "conv_wgrad_band_into");
+    m.def("conv_wgrad_ws_floats", &conv_wgrad_ws_floats,
+          "f32 elements of workspace conv_wgrad_band_into (band) or "
+          "conv_wgrad_into needs for N images at the default grid",
+          py::arg("conv_id"), py::arg("cin1"), py::arg("N"), py::arg("band"));
     m.def("conv_fwd_band", &conv_fwd_band,
           "per-image band forward (image LDS-resident; weights in LDS for "
           "conv1, in registers for the 64-output layers)",

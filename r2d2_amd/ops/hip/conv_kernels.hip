@@ -27,10 +27,14 @@
 //           launch per layer, the image's dY staged once in LDS inside a
 //           zero halo for all classes, weights in registers, dX stored
 //           through LDS; bit-equal to dense.
-// Wgrad:    dWt(COUT,K) += dY^T @ patch in 32-row tiles with f32 atomics;
-//           fused ReLU mask + bias grad; chunked (patch tiles copied from
-//           global memory) and band (whole image + its dY in LDS, fragments
-//           gathered straight from the image).  Both run WgradTile.
+// Wgrad:    dWt(COUT,K) = dY^T @ patch in 32-row tiles, register
+//           accumulators flushed once per workgroup: with f32 atomics into
+//           fresh zeros, or (_into) as a slab of partial sums that
+//           wgrad_reduce_kernel sums into .grad in torch layout; optional
+//           fused ReLU mask (empty act = dY pre-masked) + bias grad; chunked
+//           (patch tiles copied from global memory) and band (whole image +
+//           its dY in LDS, fragments gathered straight from the image).
+//           Both run WgradTile.
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -419,12 +423,12 @@ __global__ __launch_bounds__(256) void conv_dgrad_dense_kernel(
 // Wgrad: dWt(COUT, K) += sum_rows relu_mask(dY)[row][co] * patch[row][k]
 // The FULL K extent (<= 576) and full COUT (<= 64) are covered per 32-row
 // tile, so dY and the patches are each read exactly once; per-wave
-// accumulators cover all k-tiles and are flushed with f32 atomics once per
-// workgroup.  Fused ReLU mask + bias grad.
+// accumulators cover all k-tiles and are flushed once per workgroup (atomics
+// or slab, see flush / flush_slab).  Optional fused ReLU mask; bias grad.
 //
 // WgradTile is everything the chunked and the band kernel share: the wave
-// split, the accumulators, the masked dY staging, one 32-row MFMA step, the
-// bias column sum and the atomic flush.  The kernels differ only in where a
+// split, the accumulators, the dY staging, one 32-row MFMA step, the bias
+// column sum and the two flushes.  The kernels differ only in where a
 // B fragment comes from (a patch tile copied from global memory vs a gather
 // straight out of the LDS image) and in their outer loop.
 //
@@ -478,9 +482,12 @@ struct WgradTile {
         return wc * KHALF + kf * 16 + pcol;
     }
 
-    // Stage `rows` rows of dY, masked by the forward output's ReLU, with
-    // 16-byte loads: GEMM rows gm0 .. gm0+nvalid-1, zero rows after them.
+    // Stage `rows` rows of dY with 16-byte loads: GEMM rows gm0 ..
+    // gm0+nvalid-1, zero rows after them.  MASK applies the forward output's
+    // ReLU (act > 0) on the way; without it dY arrives pre-masked (the
+    // engine's dgrads mask on store) and act is never read.
     // The caller owns the barriers around it.
+    template <bool MASK>
     __device__ __forceinline__ static void stage_dy(
         __hip_bfloat16* s_dy,                    // [rows][LD_DY]
         const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
@@ -493,11 +500,13 @@ struct WgradTile {
             bf16x8 v = zero_bf16x8();
             if (mrow < nvalid) {
                 long off = (gm0 + mrow) * COUT + col;
-                bf16x8 g = load_bf16x8(dY + off);
-                bf16x8 m = load_bf16x8(act + off);
+                v = load_bf16x8(dY + off);
+                if constexpr (MASK) {
+                    bf16x8 m = load_bf16x8(act + off);
 #pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    v[e] = ((float)m[e] > 0.f) ? g[e] : (__bf16)0.f;
+                    for (int e = 0; e < 8; ++e)
+                        v[e] = ((float)m[e] > 0.f) ? v[e] : (__bf16)0.f;
+                }
             }
             *reinterpret_cast<bf16x8*>(&s_dy[mrow * LD_DY + col]) = v;
         }
@@ -554,18 +563,104 @@ struct WgradTile {
             atomicAdd(&db[threadIdx.x], s);
         }
     }
+
+    // Slab flush: the workgroup's partial sums go to its own slot of a
+    // workspace with plain stores, no atomics; wgrad_reduce_kernel sums the
+    // slots afterwards.  A slot is SLOT floats: the COUT*K accumulators in
+    // FRAGMENT order -- the f32x4 of (wave, i, kf) and lane at float4 index
+    // ((wave*2 + i)*KFRAG + kf)*64 + lane, so every wave-instruction stores
+    // one contiguous KiB -- then 64 floats of bias partials (COUT used, the
+    // rest zero).  slab_coord() maps a slot index back to (co, k).
+    static constexpr int SLOT = COUT * K + 64;
+
+    __device__ __forceinline__ void flush_slab(float* __restrict__ slot,
+                                               float* s_red) {
+        int wave = threadIdx.x / WAVE;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int kf = 0; kf < KFRAG; ++kf)
+                *reinterpret_cast<f32x4*>(
+                    slot + ((((wave * 2 + i) * KFRAG + kf) * 64 + lane) << 2)) =
+                    acc[i][kf];
+        __syncthreads();
+        s_red[threadIdx.x] = bias_acc;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            float s = 0.f;
+            if (threadIdx.x < COUT)
+                for (int i = threadIdx.x; i < 256; i += COUT) s += s_red[i];
+            slot[COUT * K + threadIdx.x] = s;
+        }
+    }
+
+    // (co, k) of float e < COUT*K of a slot: the inverse of flush_slab's
+    // order and for_each_acc's fragment layout
+    __device__ __forceinline__ static void slab_coord(int e, int& co, int& k) {
+        int r = e & 3, ln = (e >> 2) & 63, f = e >> 8;
+        int kf = f % KFRAG, i = f / KFRAG % 2, wave = f / (2 * KFRAG);
+        int wr_ = (NCOT == 1) ? 0 : (wave >> 1);
+        int wc_ = (NCOT == 1) ? wave : (wave & 1);
+        co = wr_ * 32 + i * 16 + (ln >> 4) * 4 + r;
+        k = wc_ * KHALF + kf * 16 + (ln & 15);
+    }
 };
+
+// ---------------------------------------------------------------------------
+// Reducer of the slab flush.  ws holds `parts` slots of WgradTile<G>::SLOT
+// floats; element e of the result is slot 0's e + slot 1's e + ... summed in
+// an order fixed by the code alone: thread group g of 16 adds slots g, g + 16,
+// g + 32, ... in turn, then one thread adds the 16 group sums from 0 up.  So
+// two launches on the same slots give the same bits.  A workgroup owns 64
+// consecutive floats of the slot (256 B per slot, four slots per wave load)
+// and stores them where they belong: the weight gradient in torch layout
+// (COUT, CIN, KH, KW), the last 64 floats' first COUT into db.  Destination
+// elements are OVERWRITTEN, not added to.
+// ---------------------------------------------------------------------------
+template <class G>
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(
+    const float* __restrict__ ws,   // (parts, SLOT)
+    int parts,
+    float* __restrict__ dW,         // (COUT, CIN, KH, KW)
+    float* __restrict__ db) {       // (COUT,)
+    using Tile = WgradTile<G>;
+    __shared__ __attribute__((aligned(16))) float s_part[16][64];
+    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const float* p = ws + (long)g * Tile::SLOT + blockIdx.x * 64 + q * 4;
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = g; s < parts; s += 16, p += 16L * Tile::SLOT)
+        sum += *reinterpret_cast<const f32x4*>(p);
+    *reinterpret_cast<f32x4*>(&s_part[g][q * 4]) = sum;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v += s_part[i][threadIdx.x];
+        int e = blockIdx.x * 64 + threadIdx.x;
+        if (e < G::COUT * G::K) {
+            int co, k;
+            Tile::slab_coord(e, co, k);
+            int ky = k / G::KWC, kx = k % G::KWC / G::CIN, c = k % G::CIN;
+            dW[((co * G::CIN + c) * G::KH + ky) * G::KW + kx] = v;
+        } else if (e - G::COUT * G::K < G::COUT) {
+            db[e - G::COUT * G::K] = v;
+        }
+    }
+}
 
 // chunked wgrad: a workgroup owns rows_per_chunk GEMM rows; each 32-row tile
 // of patches is copied from the global image into s_a, one barrier pair per
 // tile.
-template <class G>
+// MASK: see stage_dy.  SLAB: dWt is the partial-sum workspace and the
+// workgroup stores its slot there (flush_slab); else the atomic flush.
+template <class G, bool MASK, bool SLAB>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     const __hip_bfloat16* __restrict__ dY,   // (M, COUT)
     const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward output
     const void* __restrict__ in,             // (N, INH, INW, CIN)
-    float* __restrict__ dWt,                 // (COUT, K) f32
-    float* __restrict__ db,                  // (COUT,) f32
+    float* __restrict__ dWt,                 // (COUT, K) f32, or the slabs
+    float* __restrict__ db,                  // (COUT,) f32 (atomic flush)
     int M, int rows_per_chunk) {
     using Tile = WgradTile<G>;
     constexpr int K = G::K;
@@ -579,7 +674,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     for (long m0 = mstart; m0 < mend; m0 += 32) {
         int nvalid = (int)min(32L, mend - m0);
         __syncthreads();
-        Tile::stage_dy(s_dy, dY, act, m0, nvalid, 32);
+        Tile::template stage_dy<MASK>(s_dy, dY, act, m0, nvalid, 32);
         for (int e8 = threadIdx.x; e8 < 32 * (K / 8); e8 += 256) {
             int mrow = e8 / (K / 8);
             int k = (e8 % (K / 8)) * 8;
@@ -599,7 +694,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
         });
         tile.bias_rows(s_dy, 32);
     }
-    tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
+    if constexpr (SLAB)
+        tile.flush_slab(dWt + (long)blockIdx.x * Tile::SLOT,
+                        reinterpret_cast<float*>(s_dy));
+    else
+        tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
 }
 
 // ---------------------------------------------------------------------------
@@ -713,15 +812,15 @@ __global__ __launch_bounds__(256) void conv_fwd_band_kernel(
 // no im2col tile is ever written.  Rows past the image's last pixel gather
 // that last pixel against zero dY rows (pad, don't mask: the read needs
 // every lane active).  Each image's contribution accumulates in registers,
-// with ONE atomic flush per workgroup.
+// with ONE flush per workgroup.
 // ---------------------------------------------------------------------------
-template <class G>
+template <class G, bool MASK, bool SLAB>
 __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
     const __hip_bfloat16* __restrict__ dY,   // (M=N*NPIX, COUT)
     const __hip_bfloat16* __restrict__ act,  // (M, COUT) forward out (mask)
     const void* __restrict__ in,             // (N, INH, INW, CIN)
-    float* __restrict__ dWt,                 // (COUT, K) f32
-    float* __restrict__ db,                  // (COUT,) f32
+    float* __restrict__ dWt,                 // (COUT, K) f32, or the slabs
+    float* __restrict__ db,                  // (COUT,) f32 (atomic flush)
     int N, int imgs_per_wg) {
     using Tile = WgradTile<G>;
     using Img = GatherImage<G>;
@@ -762,7 +861,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
         for (int r0 = 0; r0 < NPIX; r0 += ROWS) {
             __syncthreads();    // the tiles staged before are done
             if (r0 == 0) stage_image<G, Img>(s_img, in, n);
-            Tile::stage_dy(s_dy, dY, act, n * NPIX + r0, NPIX - r0, ROWS);
+            Tile::template stage_dy<MASK>(s_dy, dY, act, n * NPIX + r0,
+                                          NPIX - r0, ROWS);
             __syncthreads();
             tile.bias_rows(s_dy, ROWS);
             for (int p0 = r0; p0 < min(r0 + ROWS, NPIX); p0 += 32) {
@@ -775,7 +875,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_band_kernel(
             }
         }
     }
-    tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
+    if constexpr (SLAB)
+        tile.flush_slab(dWt + (long)blockIdx.x * Tile::SLOT,
+                        reinterpret_cast<float*>(s_dy));
+    else
+        tile.flush(dWt, db, reinterpret_cast<float*>(s_dy));
 }
 
 // ---------------------------------------------------------------------------
@@ -1264,16 +1368,56 @@ static void check_weights(const torch::Tensor& Wt, const char* who) {
 template <class G>
 static void check_grads(const torch::Tensor& dY, const torch::Tensor& act,
                         int64_t N, const char* who) {
-    TORCH_CHECK(dY.numel() == N * G::NPIX * G::COUT
-                && act.numel() == dY.numel(), who, ": dY/act must be (N*",
-                G::NPIX, ", ", G::COUT, ")");
+    // an empty act = no mask: dY is pre-masked (as gemm_dgrad's convention)
+    bool has_m = act.defined() && act.numel() > 0;
+    TORCH_CHECK(N > 0 && dY.numel() == N * G::NPIX * G::COUT
+                && (!has_m || act.numel() == dY.numel()), who,
+                ": dY and a non-empty act must be (N*", G::NPIX, ", ", G::COUT,
+                "), got ", dY.sizes(), " and ", act.sizes());
     // rows are staged with 16-byte loads
     for (const torch::Tensor* t : {&dY, &act})
-        TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16
-                    && t->is_contiguous()
-                    && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+        TORCH_CHECK((t == &act && !has_m)
+                    || (t->is_cuda() && t->dtype() == torch::kBFloat16
+                        && t->is_contiguous()
+                        && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0),
                     who, ": dY/act must be contiguous, 16-byte aligned bf16 "
                     "device tensors");
+}
+
+// Destination of the slab path: the partial-sum workspace (at least `parts`
+// slots) and the .grad views the reducer overwrites, in torch layout.
+template <class G>
+static void check_wgrad_dest(const torch::Tensor& ws, const torch::Tensor& dW,
+                             const torch::Tensor& db, int parts,
+                             const char* who) {
+    constexpr long SLOT = WgradTile<G>::SLOT;
+    TORCH_CHECK(ws.is_cuda() && ws.dtype() == torch::kFloat32
+                && ws.is_contiguous()
+                && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0
+                && ws.numel() >= parts * SLOT, who,
+                ": the workspace must be a contiguous, 16-byte aligned f32 "
+                "device tensor of at least ", parts, " x ", SLOT,
+                " elements, got ", ws.numel());
+    TORCH_CHECK(dW.is_cuda() && dW.dtype() == torch::kFloat32
+                && dW.is_contiguous() && dW.dim() == 4
+                && dW.size(0) == G::COUT && dW.size(1) == G::CIN
+                && dW.size(2) == G::KH && dW.size(3) == G::KW, who,
+                ": dW must be a contiguous f32 device tensor (", G::COUT, ", ",
+                G::CIN, ", ", G::KH, ", ", G::KW, "), got ", dW.sizes());
+    TORCH_CHECK(db.is_cuda() && db.dtype() == torch::kFloat32
+                && db.is_contiguous() && db.dim() == 1
+                && db.size(0) == G::COUT, who,
+                ": db must be a contiguous f32 device tensor (", G::COUT, ")");
+}
+
+template <class G>
+static void launch_wgrad_reduce(const torch::Tensor& ws, int parts,
+                                const torch::Tensor& dW,
+                                const torch::Tensor& db) {
+    hipLaunchKernelGGL(
+        (wgrad_reduce_kernel<G>), dim3(WgradTile<G>::SLOT / 64), dim3(256), 0,
+        at::cuda::getCurrentCUDAStream().stream(), ws.data_ptr<float>(), parts,
+        dW.data_ptr<float>(), db.data_ptr<float>());
 }
 
 // the geometry arguments of the classic entry points must name the layer
@@ -1547,36 +1691,136 @@ torch::Tensor conv_dgrad_band(torch::Tensor dY, torch::Tensor Wd,
     return dX;
 }
 
-// per-image band wgrad (see conv_wgrad_band_kernel).  N = number of images.
-std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
-                                           torch::Tensor in, int64_t conv_id,
-                                           int64_t N) {
-    const char* who = "conv_wgrad_band";
+
+// ---------------------------------------------------------------------------
+// Wgrad entry points.  Each kernel has two: the returning one (fresh zeros,
+// atomic flush, {dWt (COUT, K) packed, db}) and the _into one (slab flush
+// into the caller's workspace, then wgrad_reduce_kernel OVERWRITES dW in
+// torch layout and db; no zeros, no temporaries, bitwise reproducible).  An
+// empty act selects MASK = false in both.  WgradDest is null for the first.
+// ---------------------------------------------------------------------------
+struct WgradDest {
+    const torch::Tensor &ws, &dW, &db;
+};
+
+// grid of the band wgrad.  512 workgroups = the 2 per CU that VGPRs
+// (conv2/conv3) or LDS (conv1) allow, times 256 CUs: one resident round with
+// no tail, and every workgroup fewer is COUT*K flushed floats fewer.
+// Measured for 5440 images, atomic flush, 1024 / 512 / 256 workgroups: conv3
+// 162 / 122 / 121 us, conv2 170 / 129 / 145, conv1 (4 ch) 217 / 193 / 334.
+static void wgrad_band_grid(int64_t N, int64_t max_wgs, int& imgs, int& grid) {
+    band_grid(N, max_wgs > 0 ? max_wgs : BAND_WGS, imgs, grid);
+}
+
+static std::vector<torch::Tensor> wgrad_band_run(
+    const char* who, const torch::Tensor& dY, const torch::Tensor& act,
+    const torch::Tensor& in, int64_t conv_id, int64_t N, int64_t max_wgs,
+    const WgradDest* dest) {
     torch::Tensor dWt, db;
+    TORCH_CHECK(N > 0 && max_wgs >= 0, who, ": N must be positive and max_wgs "
+                "non-negative");
     // whole-image staging loads 8 bytes per lane for both conv1 variants
     int cin1 = conv1_cin(conv_id, in, N, 8, 8, who);
     dispatch_layer(conv_id, cin1, who, [&](auto g) {
         using G = decltype(g);
         check_input<G>(in, N, who);
         check_grads<G>(dY, act, N, who);
-        dWt =
-            torch::zeros({G::COUT, G::K}, dY.options().dtype(torch::kFloat32));
-        db = torch::zeros({G::COUT}, dY.options().dtype(torch::kFloat32));
-        // 512 workgroups = the 2 per CU that VGPRs (conv2/conv3) or LDS
-        // (conv1) allow, times 256 CUs: one resident round with no tail,
-        // and every workgroup fewer is COUT*K atomics fewer in the flush.
-        // Measured for 5440 images, 1024 / 512 / 256 workgroups: conv3
-        // 162 / 122 / 121 us, conv2 170 / 129 / 145, conv1 (4 ch) 217 / 193
-        // / 334.
-        int imgs = cdiv(N, 512);
-        int grid = cdiv(N, imgs);
-        hipLaunchKernelGGL(
-            (conv_wgrad_band_kernel<G>), dim3(grid), dim3(256), 0,
-            at::cuda::getCurrentCUDAStream().stream(),
-            reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
-            reinterpret_cast<const __hip_bfloat16*>(act.data_ptr()),
-            in.data_ptr(), dWt.data_ptr<float>(), db.data_ptr<float>(), (int)N,
-            imgs);
+        int imgs, grid;
+        wgrad_band_grid(N, max_wgs, imgs, grid);
+        if (dest) check_wgrad_dest<G>(dest->ws, dest->dW, dest->db, grid, who);
+        bool mask = act.numel() > 0;
+        auto launch = [&](auto kernel, float* w, float* b) {
+            hipLaunchKernelGGL(
+                kernel, dim3(grid), dim3(256), 0,
+                at::cuda::getCurrentCUDAStream().stream(),
+                reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+                mask ? reinterpret_cast<const __hip_bfloat16*>(act.data_ptr())
+                     : nullptr,
+                in.data_ptr(), w, b, (int)N, imgs);
+        };
+        if (dest) {
+            float* w = dest->ws.data_ptr<float>();
+            if (mask) launch(conv_wgrad_band_kernel<G, true, true>, w, nullptr);
+            else launch(conv_wgrad_band_kernel<G, false, true>, w, nullptr);
+            launch_wgrad_reduce<G>(dest->ws, grid, dest->dW, dest->db);
+        } else {
+            auto f32 = dY.options().dtype(torch::kFloat32);
+            dWt = torch::zeros({G::COUT, G::K}, f32);
+            db = torch::zeros({G::COUT}, f32);
+            float *w = dWt.data_ptr<float>(), *b = db.data_ptr<float>();
+            if (mask) launch(conv_wgrad_band_kernel<G, true, false>, w, b);
+            else launch(conv_wgrad_band_kernel<G, false, false>, w, b);
+        }
+    });
+    return {dWt, db};
+}
+
+// per-image band wgrad (see conv_wgrad_band_kernel).  N = number of images;
+// max_wgs > 0 caps the grid (tests push several images through a workgroup).
+std::vector<torch::Tensor> conv_wgrad_band(torch::Tensor dY, torch::Tensor act,
+                                           torch::Tensor in, int64_t conv_id,
+                                           int64_t N, int64_t max_wgs) {
+    return wgrad_band_run("conv_wgrad_band", dY, act, in, conv_id, N, max_wgs,
+                          nullptr);
+}
+
+void conv_wgrad_band_into(torch::Tensor dY, torch::Tensor act,
+                          torch::Tensor in, int64_t conv_id, int64_t N,
+                          torch::Tensor ws, torch::Tensor dW, torch::Tensor db,
+                          int64_t max_wgs) {
+    WgradDest dest{ws, dW, db};
+    wgrad_band_run("conv_wgrad_band_into", dY, act, in, conv_id, N, max_wgs,
+                   &dest);
+}
+
+// GEMM rows per workgroup of the chunked wgrad: about 1024 workgroups, whole
+// 32-row tiles
+static long wgrad_chunk_rows(long M) {
+    long target_chunks = 1024;
+    long rows = std::max(32L, (M + target_chunks - 1) / target_chunks);
+    return ((rows + 31) / 32) * 32;
+}
+
+static std::vector<torch::Tensor> wgrad_chunked_run(
+    const char* who, const torch::Tensor& dY, const torch::Tensor& act,
+    const torch::Tensor& in, int64_t conv_id, int64_t N, int64_t INH,
+    int64_t INW, int64_t OH, int64_t OW, int64_t COUT, int64_t K,
+    const WgradDest* dest) {
+    torch::Tensor dWt, db;
+    TORCH_CHECK(N > 0, who, ": N must be positive");
+    int cin1 = conv1_cin(conv_id, in, N, 4, 8, who);
+    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+        using G = decltype(g);
+        check_geometry<G>(INH, INW, OH, OW, COUT, K, who);
+        check_input<G>(in, N, who);
+        check_grads<G>(dY, act, N, who);
+        long M = N * G::NPIX;
+        long rows_per_chunk = wgrad_chunk_rows(M);
+        int grid = cdiv(M, rows_per_chunk);
+        if (dest) check_wgrad_dest<G>(dest->ws, dest->dW, dest->db, grid, who);
+        bool mask = act.numel() > 0;
+        auto launch = [&](auto kernel, float* w, float* b) {
+            hipLaunchKernelGGL(
+                kernel, dim3(grid), dim3(256), 0,
+                at::cuda::getCurrentCUDAStream().stream(),
+                reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
+                mask ? reinterpret_cast<const __hip_bfloat16*>(act.data_ptr())
+                     : nullptr,
+                in.data_ptr(), w, b, (int)M, (int)rows_per_chunk);
+        };
+        if (dest) {
+            float* w = dest->ws.data_ptr<float>();
+            if (mask) launch(conv_wgrad_kernel<G, true, true>, w, nullptr);
+            else launch(conv_wgrad_kernel<G, false, true>, w, nullptr);
+            launch_wgrad_reduce<G>(dest->ws, grid, dest->dW, dest->db);
+        } else {
+            auto f32 = dY.options().dtype(torch::kFloat32);
+            dWt = torch::zeros({G::COUT, G::K}, f32);
+            db = torch::zeros({G::COUT}, f32);
+            float *w = dWt.data_ptr<float>(), *b = db.data_ptr<float>();
+            if (mask) launch(conv_wgrad_kernel<G, true, false>, w, b);
+            else launch(conv_wgrad_kernel<G, false, false>, w, b);
+        }
     });
     return {dWt, db};
 }
@@ -1586,29 +1830,31 @@ std::vector<torch::Tensor> conv_wgrad(torch::Tensor dY, torch::Tensor act,
                                       int64_t N, int64_t INH, int64_t INW,
                                       int64_t OH, int64_t OW, int64_t COUT,
                                       int64_t K) {
-    const char* who = "conv_wgrad";
-    torch::Tensor dWt, db;
-    int cin1 = conv1_cin(conv_id, in, N, 4, 8, who);
-    dispatch_layer(conv_id, cin1, who, [&](auto g) {
+    return wgrad_chunked_run("conv_wgrad", dY, act, in, conv_id, N, INH, INW,
+                             OH, OW, COUT, K, nullptr);
+}
+
+void conv_wgrad_into(torch::Tensor dY, torch::Tensor act, torch::Tensor in,
+                     int64_t conv_id, int64_t N, int64_t INH, int64_t INW,
+                     int64_t OH, int64_t OW, int64_t COUT, int64_t K,
+                     torch::Tensor ws, torch::Tensor dW, torch::Tensor db) {
+    WgradDest dest{ws, dW, db};
+    wgrad_chunked_run("conv_wgrad_into", dY, act, in, conv_id, N, INH, INW, OH,
+                      OW, COUT, K, &dest);
+}
+
+// floats of workspace an _into entry point needs for N images at its default
+// grid: band = conv_wgrad_band_into, else conv_wgrad_into
+int64_t conv_wgrad_ws_floats(int64_t conv_id, int64_t cin1, int64_t N,
+                             bool band) {
+    int64_t n = 0;
+    TORCH_CHECK(N > 0, "conv_wgrad_ws_floats: N must be positive");
+    dispatch_layer(conv_id, (int)cin1, "conv_wgrad_ws_floats", [&](auto g) {
         using G = decltype(g);
-        check_geometry<G>(INH, INW, OH, OW, COUT, K, who);
-        check_input<G>(in, N, who);
-        check_grads<G>(dY, act, N, who);
-        long M = N * G::NPIX;
-        dWt =
-            torch::zeros({G::COUT, G::K}, dY.options().dtype(torch::kFloat32));
-        db = torch::zeros({G::COUT}, dY.options().dtype(torch::kFloat32));
-        long target_chunks = 1024;
-        long rows_per_chunk =
-            std::max(32L, (M + target_chunks - 1) / target_chunks);
-        rows_per_chunk = ((rows_per_chunk + 31) / 32) * 32;
-        hipLaunchKernelGGL(
-            (conv_wgrad_kernel<G>), dim3(cdiv(M, rows_per_chunk)), dim3(256),
-            0, at::cuda::getCurrentCUDAStream().stream(),
-            reinterpret_cast<const __hip_bfloat16*>(dY.data_ptr()),
-            reinterpret_cast<const __hip_bfloat16*>(act.data_ptr()),
-            in.data_ptr(), dWt.data_ptr<float>(), db.data_ptr<float>(), (int)M,
-            (int)rows_per_chunk);
+        int imgs, grid;
+        wgrad_band_grid(N, 0, imgs, grid);
+        if (!band) grid = cdiv(N * G::NPIX, wgrad_chunk_rows(N * G::NPIX));
+        n = (int64_t)grid * WgradTile<G>::SLOT;
     });
-    return {dWt, db};
+    return n;
 }
