@@ -205,7 +205,8 @@ PRESETS = {
     ),
     # `cartpole` on the HIP engine: the 512-wide MLP encoder and LSTM are the
     # one vector-observation shape the engine serves (ops/engine.py
-    # mlp_config_error).  Host replay: the GPU replay stores uint8 frames only
+    # mlp_config_error).  Host replay; `cartpole_hip_gpu_replay` below is the
+    # same config over the GPU replay's float row store
     "cartpole_hip": dict(
         game_name="CartPole", env_type="cartpole", obs_shape=(4,),
         action_dim=2, encoder="mlp", hidden_dim=512, mlp_hidden=512,
@@ -213,6 +214,19 @@ PRESETS = {
         buffer_capacity=40_000, learning_starts=2_000, block_length=40,
         burn_in_steps=8, learning_steps=8, forward_steps=3,
         training_steps=2_000, num_actors=2, amp=True,
+    ),
+    # `cartpole_hip` in the learner-owns-the-replay topology: (D,) float32
+    # rows in the GPU replay (replay/gpu_replay.py), sampling, gather and
+    # priority write-back on the device, one GPU VectorActor stepping 16 envs
+    # and fed over the WeightBus
+    "cartpole_hip_gpu_replay": dict(
+        game_name="CartPole", env_type="cartpole", obs_shape=(4,),
+        action_dim=2, encoder="mlp", hidden_dim=512, mlp_hidden=512,
+        device="cuda", dtype="bf16", use_hip_kernels=True, gpu_replay=True,
+        buffer_capacity=40_000, learning_starts=2_000, block_length=40,
+        burn_in_steps=8, learning_steps=8, forward_steps=3,
+        training_steps=2_000, amp=True,
+        vector_actors=True, actor_device="cuda", num_actors=16,
     ),
     # `mspacman` with the GPU replay in frame-once mode — the preset
     # bench.py takes to time the dedup gather in the full learner loop.

@@ -40,6 +40,13 @@ std::vector<torch::Tensor> replay_gather_batch_dedup(
     torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
     torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
     int64_t max_learn, int64_t H, int64_t spb, int64_t C);
+std::vector<torch::Tensor> replay_gather_batch_vec(
+    torch::Tensor obs_store, torch::Tensor la_store, torch::Tensor lr_store,
+    torch::Tensor act_store, torch::Tensor nsr_store, torch::Tensor gam_store,
+    torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
+    torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
+    int64_t max_learn, int64_t H, int64_t spb,
+    c10::optional<std::vector<torch::Tensor>> out);
 
 // gemm_kernels.hip
 torch::Tensor gemm_bias_act(torch::Tensor A, torch::Tensor Wt,
@@ -199,6 +206,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "replay_gather_batch from the frame-once store: one (H, W) frame "
           "per step, obs_rows + C - 1 frames per slot; the (B, T, H*W*C) HWC "
           "stacks are rebuilt in the gather");
+    m.def("replay_gather_batch_vec", &replay_gather_batch_vec,
+          "replay_gather_batch from the float row store of vector "
+          "observations: obs store (num_blocks, obs_rows, D) f32, obs_out "
+          "(B, T, D) f32, one workgroup per sample copying its contiguous "
+          "span; `out` = the eight outputs preallocated by the caller",
+          py::arg("obs_store"), py::arg("la_store"), py::arg("lr_store"),
+          py::arg("act_store"), py::arg("nsr_store"), py::arg("gam_store"),
+          py::arg("hid_store"), py::arg("idx"), py::arg("meta"),
+          py::arg("seg"), py::arg("weights"), py::arg("T"), py::arg("A"),
+          py::arg("max_learn"), py::arg("H"), py::arg("spb"),
+          py::arg("out") = py::none());
     // path: 0 automatic, 64 the unstaged 64x64 kernel, 6464 / 12864 the
     // LDS-staged 64x64 / 128x64 instantiations (tests and tools force one)
     m.def("gemm_bias_act", &gemm_bias_act, "MFMA GEMM + bias + activation",

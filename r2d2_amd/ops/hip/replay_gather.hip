@@ -183,6 +183,60 @@ __global__ void gather_frames_stack_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Kernel B'': padded sequence tensors from the float row store (vector
+//   observations, D float32 per step).  A (sample, time) row is at most a few
+//   dozen bytes, so a grid of B * T workgroups as in Kernel B would be all
+//   launch and no copy.  The valid rows of one sample are CONTIGUOUS in the
+//   store — obs_start - burn .. + valid, inside one slot — so grid.x = B and
+//   each workgroup reads its five metadata words once and copies one span:
+//     obs_out[b*T*D + i] = obs_store[(obs_start - burn)*D + i],  i < valid*D
+//   and zero-fills i = valid*D .. T*D.  kVec4 (D % 4 == 0 and both bases
+//   16-byte aligned; every row offset is then a multiple of 16 bytes) moves
+//   float4, otherwise one float per thread-iteration.  la_out / lr_out as in
+//   Kernel B.  A span that is not wholly inside the store (corrupt metadata)
+//   pads as if valid = 0, the guard of Kernel B'.
+// ---------------------------------------------------------------------------
+template <bool kVec4>
+__global__ void gather_rows_f32_kernel(
+    const float* __restrict__ obs_store,          // (num_blocks, obs_rows, D)
+    const unsigned char* __restrict__ la_store,   // (num_blocks, obs_rows)
+    const float* __restrict__ lr_store,           // (num_blocks, obs_rows)
+    const int* __restrict__ meta,                 // (5, B)
+    float* __restrict__ obs_out,                  // (B, T, D)
+    float* __restrict__ la_out,                   // (B, T, A)
+    float* __restrict__ lr_out,                   // (B, T)
+    int B, int T, int A, long D, long total_rows) {
+    int b = blockIdx.x;
+    long burn = meta[0 * B + b], learn = meta[1 * B + b], fwd = meta[2 * B + b];
+    long g0 = (long)meta[3 * B + b] - burn;  // first global row of the span
+    long valid = burn + learn + fwd;
+    if (valid > T) valid = T;                // Kernel B copies t < T only
+    if (burn < 0 || learn < 0 || fwd < 0 || g0 < 0 || g0 + valid > total_rows) {
+        valid = 0;
+        g0 = 0;
+    }
+    const float* src = obs_store + g0 * D;
+    float* dst = obs_out + (long)b * T * D;
+    long n = valid * D, total = (long)T * D;
+    if (kVec4) {
+        const float4* src4 = reinterpret_cast<const float4*>(src);
+        float4* dst4 = reinterpret_cast<float4*>(dst);
+        for (long i = threadIdx.x; i < total / 4; i += blockDim.x)
+            dst4[i] = (i < n / 4) ? src4[i] : float4{0.f, 0.f, 0.f, 0.f};
+    } else {
+        for (long i = threadIdx.x; i < total; i += blockDim.x)
+            dst[i] = (i < n) ? src[i] : 0.f;
+    }
+    for (long t = threadIdx.x; t < T; t += blockDim.x)
+        lr_out[(long)b * T + t] = (t < valid) ? lr_store[g0 + t] : 0.f;
+    for (long i = threadIdx.x; i < (long)T * A; i += blockDim.x) {
+        long t = i / A, a = i % A;
+        la_out[(long)b * T * A + i] =
+            (t < valid && la_store[g0 + t] == a) ? 1.f : 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Kernel C: flat per-learning-step arrays + hidden states + repeated weights.
 //   grid over B * max_learn threads.
 // ---------------------------------------------------------------------------
@@ -432,6 +486,142 @@ std::vector<torch::Tensor> replay_gather_batch_dedup(
                        meta.data_ptr<int>(), obs_out.data_ptr<unsigned char>(),
                        la_out.data_ptr<float>(), lr_out.data_ptr<float>(),
                        B, (int)T, (int)A, (int)C, HW, obs_rows, num_blocks);
+
+    int total = B * (int)max_learn;
+    hipLaunchKernelGGL(gather_flat_kernel, dim3((total + 255) / 256), dim3(256),
+                       0, stream.stream(), act_store.data_ptr<unsigned char>(),
+                       nsr_store.data_ptr<float>(), gam_store.data_ptr<float>(),
+                       hid_store.data_ptr<float>(), idx.data_ptr<long>(),
+                       meta.data_ptr<int>(), seg.data_ptr<int>(),
+                       weights.data_ptr<float>(), act_out.data_ptr<long>(),
+                       nsr_out.data_ptr<float>(), gam_out.data_ptr<float>(),
+                       w_out.data_ptr<float>(), hid_out.data_ptr<float>(),
+                       B, (int)max_learn, (int)H, block_len, (int)spb);
+
+    return {obs_out, la_out, lr_out, act_out, nsr_out, gam_out, w_out, hid_out};
+}
+
+// Float row store (vector observations): same outputs as replay_gather_batch
+// with obs_out (B, T, D) float32, copied by gather_rows_f32_kernel, one
+// workgroup per sample.  `out`, when given, holds the eight output tensors
+// preallocated by the caller (contiguous, shapes as returned); they are
+// checked like the inputs and nothing is written before every check passed.
+std::vector<torch::Tensor> replay_gather_batch_vec(
+    torch::Tensor obs_store, torch::Tensor la_store, torch::Tensor lr_store,
+    torch::Tensor act_store, torch::Tensor nsr_store, torch::Tensor gam_store,
+    torch::Tensor hid_store, torch::Tensor idx, torch::Tensor meta,
+    torch::Tensor seg, torch::Tensor weights, int64_t T, int64_t A,
+    int64_t max_learn, int64_t H, int64_t spb,
+    c10::optional<std::vector<torch::Tensor>> out) {
+    TORCH_CHECK(obs_store.is_cuda() && la_store.is_cuda() && lr_store.is_cuda()
+                && act_store.is_cuda() && nsr_store.is_cuda()
+                && gam_store.is_cuda() && hid_store.is_cuda() && idx.is_cuda()
+                && meta.is_cuda() && seg.is_cuda() && weights.is_cuda(),
+                "replay_gather_batch_vec: every tensor must be on the GPU");
+    TORCH_CHECK(obs_store.dtype() == torch::kFloat32,
+                "replay_gather_batch_vec: the obs store must be float32");
+    TORCH_CHECK(la_store.dtype() == torch::kUInt8
+                && act_store.dtype() == torch::kUInt8,
+                "replay_gather_batch_vec: la/act stores must be uint8");
+    TORCH_CHECK(lr_store.dtype() == torch::kFloat32
+                && nsr_store.dtype() == torch::kFloat32
+                && gam_store.dtype() == torch::kFloat32
+                && hid_store.dtype() == torch::kFloat32
+                && weights.dtype() == torch::kFloat32,
+                "replay_gather_batch_vec: lr/nsr/gam/hid/weights must be "
+                "float32");
+    TORCH_CHECK(idx.dtype() == torch::kInt64 && meta.dtype() == torch::kInt32
+                && seg.dtype() == torch::kInt32,
+                "replay_gather_batch_vec: idx int64, meta/seg int32");
+    TORCH_CHECK(obs_store.is_contiguous() && la_store.is_contiguous()
+                && lr_store.is_contiguous() && act_store.is_contiguous()
+                && nsr_store.is_contiguous() && gam_store.is_contiguous()
+                && hid_store.is_contiguous() && idx.is_contiguous()
+                && meta.is_contiguous() && seg.is_contiguous()
+                && weights.is_contiguous(),
+                "replay_gather_batch_vec: every tensor must be contiguous");
+    TORCH_CHECK(obs_store.dim() == 3 && la_store.dim() == 2
+                && lr_store.dim() == 2 && act_store.dim() == 2
+                && idx.dim() == 1,
+                "replay_gather_batch_vec: obs store (num_blocks, obs_rows, D),"
+                " la/lr/act stores 2-d, idx 1-d");
+    TORCH_CHECK(obs_store.size(0) == la_store.size(0)
+                && obs_store.size(1) == la_store.size(1)
+                && lr_store.sizes() == la_store.sizes()
+                && act_store.size(0) == la_store.size(0)
+                && nsr_store.sizes() == act_store.sizes()
+                && gam_store.sizes() == act_store.sizes(),
+                "replay_gather_batch_vec: store shapes disagree");
+    int64_t B64 = idx.size(0);
+    TORCH_CHECK(B64 >= 1 && B64 <= 1024, "replay_gather_batch_vec: B must be "
+                "in [1, 1024], got ", B64);
+    int B = (int)B64;
+    long D = obs_store.size(2);
+    TORCH_CHECK(D >= 1, "replay_gather_batch_vec: D must be >= 1, got ", D);
+    TORCH_CHECK(A >= 1 && A <= 256, "replay_gather_batch_vec: A must be in "
+                "[1, 256], got ", A);
+    TORCH_CHECK(meta.dim() == 2 && meta.size(0) == 5 && meta.size(1) == B
+                && seg.numel() == B + 1 && weights.numel() == B,
+                "replay_gather_batch_vec: meta (5, B), seg (B + 1,), "
+                "weights (B,)");
+    TORCH_CHECK(T >= 1 && max_learn >= 1 && H >= 1 && spb >= 1);
+    TORCH_CHECK(T * D < (1L << 31) && T * A < (1L << 31)
+                && (long)B * max_learn < (1L << 31));
+    TORCH_CHECK(hid_store.dim() == 2 && hid_store.size(1) == 2 * H
+                && hid_store.size(0) == la_store.size(0) * spb,
+                "replay_gather_batch_vec: hid store must be "
+                "(num_blocks * spb, 2 * H)");
+    long total_rows = obs_store.size(0) * obs_store.size(1);
+    long block_len = act_store.size(1);
+    long Rmax = (long)B * max_learn;
+    auto f32 = lr_store.options();
+    auto i64 = idx.options();
+    torch::Tensor obs_out, la_out, lr_out, act_out, nsr_out, gam_out, w_out,
+        hid_out;
+    if (out.has_value()) {
+        auto& o = *out;
+        TORCH_CHECK(o.size() == 8, "replay_gather_batch_vec: out must hold the"
+                    " eight output tensors, got ", o.size());
+        const std::vector<int64_t> shapes[8] = {
+            {B, T, D}, {B, T, A}, {B, T}, {Rmax}, {Rmax}, {Rmax}, {Rmax},
+            {2, B, H}};
+        for (int k = 0; k < 8; ++k) {
+            TORCH_CHECK(o[k].is_cuda() && o[k].is_contiguous()
+                        && o[k].dtype() == (k == 3 ? torch::kInt64
+                                                   : torch::kFloat32)
+                        && o[k].sizes() == c10::IntArrayRef(shapes[k]),
+                        "replay_gather_batch_vec: out[", k, "] must be a "
+                        "contiguous GPU tensor of the returned shape and "
+                        "dtype");
+        }
+        obs_out = o[0]; la_out = o[1]; lr_out = o[2]; act_out = o[3];
+        nsr_out = o[4]; gam_out = o[5]; w_out = o[6]; hid_out = o[7];
+    } else {
+        obs_out = torch::empty({B, T, D}, f32);
+        la_out = torch::empty({B, T, A}, f32);
+        lr_out = torch::empty({B, T}, f32);
+        act_out = torch::empty({Rmax}, i64);
+        nsr_out = torch::empty({Rmax}, f32);
+        gam_out = torch::empty({Rmax}, f32);
+        w_out = torch::empty({Rmax}, f32);
+        hid_out = torch::empty({2, B, H}, f32);
+    }
+    auto stream = at::cuda::getCurrentCUDAStream();
+
+    // 16-byte moves need D % 4 == 0 (every row offset a multiple of 16 bytes)
+    // and both bases aligned: allocator bases are, a caller's view may not be
+    bool vec4 = D % 4 == 0
+        && reinterpret_cast<uintptr_t>(obs_store.data_ptr<float>()) % 16 == 0
+        && reinterpret_cast<uintptr_t>(obs_out.data_ptr<float>()) % 16 == 0;
+    auto rows = vec4 ? gather_rows_f32_kernel<true>
+                     : gather_rows_f32_kernel<false>;
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), 0, stream.stream(),
+                       obs_store.data_ptr<float>(),
+                       la_store.data_ptr<unsigned char>(),
+                       lr_store.data_ptr<float>(), meta.data_ptr<int>(),
+                       obs_out.data_ptr<float>(), la_out.data_ptr<float>(),
+                       lr_out.data_ptr<float>(), B, (int)T, (int)A, D,
+                       total_rows);
 
     int total = B * (int)max_learn;
     hipLaunchKernelGGL(gather_flat_kernel, dim3((total + 255) / 256), dim3(256),

@@ -16,6 +16,13 @@ With ``config.replay_frame_dedup`` the store keeps ONE (H, W) frame per step
 (replay/frame_dedup.py) — and the gather kernel rebuilds the HWC stacks, so
 the sampled batch is the same in both modes at a quarter of the obs bytes in
 HBM, in pinned staging and over H2D.
+
+Vector observations (a 1-D ``obs_shape`` of width D, e.g. CartPole) get a
+float32 row store, (num_blocks, obs_rows, D): ingest casts the block's rows
+to float32 into the pinned buffer, and the gather copies each sample's
+contiguous span of rows with one workgroup (replay_gather_batch_vec).  The
+sampled ``obs`` is (B, T, D) float32; everything else is shared with the
+frame stores.
 """
 
 from typing import Optional
@@ -34,7 +41,10 @@ class GpuReplayBuffer:
         c = cfg.get()
         self.cfg = c
         self.device = torch.device(device)
-        assert len(c.obs_shape) == 3, "GPU replay stores uint8 frames"
+        assert len(c.obs_shape) in (1, 3), \
+            "GPU replay stores uint8 frames or float32 vector rows"
+        # (D,) vector observations: a float32 row store, no frames
+        self.vector_obs = len(c.obs_shape) == 1
         self.obs_shape = tuple(c.obs_shape)
         self.frame_bytes = int(np.prod(self.obs_shape))
         self.A = c.action_dim
@@ -57,7 +67,12 @@ class GpuReplayBuffer:
         self.dedup_verify = bool(c.replay_dedup_verify)
         dev = self.device
         nb, spb = self.num_blocks, self.spb
-        if self.frame_dedup:
+        if self.vector_obs:
+            # one (D,) float32 row per step; the valid rows of a sequence
+            # are contiguous, which the gather kernel copies as one span
+            self.obs_store = torch.zeros(nb, self.obs_rows, self.obs_shape[0],
+                                         dtype=torch.float32, device=dev)
+        elif self.frame_dedup:
             # one frame per step: slot = (C - 1) lead-in frames of its first
             # stack + one frame per row, so row r's stack is frames
             # r .. r + C - 1 of its own slot
@@ -109,7 +124,8 @@ class GpuReplayBuffer:
         self._n_pin = 4
         self._pin_obs = [torch.empty(self.obs_store.shape[1],
                                      self.obs_store.shape[-1],
-                                     dtype=torch.uint8, pin_memory=True)
+                                     dtype=self.obs_store.dtype,
+                                     pin_memory=True)
                          for _ in range(self._n_pin)]
         self._pin_ev = [torch.cuda.Event() for _ in range(self._n_pin)]
         self._pin_used = [False] * self._n_pin
@@ -152,7 +168,13 @@ class GpuReplayBuffer:
         nseq = block.num_sequences
         dev = self.device
 
-        if self.frame_dedup:
+        if self.vector_obs:
+            # float row store: no transpose; any real dtype (the uint8 rows
+            # of bench.build_synthetic_block too) is cast to float32 on its
+            # way into the pinned buffer below
+            assert block.obs.shape[1:] == self.obs_shape
+            nframes = rows
+        elif self.frame_dedup:
             # frame-once store: no transpose, rows + C - 1 frames written
             # straight into the pinned buffer below; the gather kernel
             # rebuilds the HWC stacks
@@ -185,7 +207,9 @@ class GpuReplayBuffer:
         if self._pin_used[pi]:
             self._pin_ev[pi].synchronize()
         pin = self._pin_obs[pi]
-        if self.frame_dedup:
+        if self.vector_obs:
+            np.copyto(pin[:rows].numpy(), block.obs, casting="unsafe")
+        elif self.frame_dedup:
             frames_from_stacked(
                 block.obs,
                 out=pin[:nframes].numpy().reshape(
@@ -280,7 +304,13 @@ class GpuReplayBuffer:
             meta, seg = self._ext.replay_gather_meta(
                 idx, self.burn_s, self.learn_s, self.fwd_s, self.obs_start_s,
                 self.learn_off_s, self.spb)
-            if self.frame_dedup:
+            if self.vector_obs:
+                outs = self._ext.replay_gather_batch_vec(
+                    self.obs_store, self.la_store, self.lr_store,
+                    self.act_store, self.nsr_store, self.gam_store,
+                    self.hid_store, idx, meta, seg, weight, self.T, self.A,
+                    self.learn_len, self.H, self.spb)
+            elif self.frame_dedup:
                 outs = self._ext.replay_gather_batch_dedup(
                     self.obs_store, self.la_store, self.lr_store,
                     self.act_store, self.nsr_store, self.gam_store,
@@ -314,9 +344,13 @@ class GpuReplayBuffer:
         obs, la, lr, act, nsr, gam, w_rep, hid = outs
         B = idx.shape[0]
         R = int(seg_h[-1])
-        c_, h_, w_ = self.obs_shape
+        if self.vector_obs:
+            obs = obs.view(B, self.T, self.obs_shape[0])   # float32 rows
+        else:
+            c_, h_, w_ = self.obs_shape
+            obs = obs.view(B, self.T, h_, w_, c_)   # HWC layout
         batch = TrainingBatch(
-            obs=obs.view(B, self.T, h_, w_, c_),   # HWC layout
+            obs=obs,
             last_action=la, last_reward=lr, hidden=hid,
             action=act[:R].unsqueeze(1), n_step_reward=nsr[:R], gamma=gam[:R],
             burn_in_steps=meta_h[0].long(), learning_steps=meta_h[1].long(),

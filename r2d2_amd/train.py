@@ -101,8 +101,10 @@ def train(seed: int = 0, restart_dead_actors: bool = True,
     use_gpu_replay = c.gpu_replay and torch.cuda.is_available()
     learner = Learner(batch_queue, priority_queue, model,
                       model_dir=model_dir)
-    # vector-observation configs the engine serves train on it over the HOST
-    # replay (the GPU replay stores uint8 frames only)
+    # vector-observation configs the engine serves train on it over either
+    # replay: the host ReplayBuffer, or with gpu_replay the GPU replay's
+    # float row store (widths the engine does not serve then train through
+    # the eager train_step with the fused loss kernels)
     from .ops.engine import mlp_supported
     mlp_engine = (mlp_supported(c) and c.device == "cuda"
                   and torch.cuda.is_available())
