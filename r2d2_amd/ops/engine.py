@@ -28,9 +28,19 @@ from .. import config as cfg
 from ..models.encoders import ImpalaCNN, MLPEncoder
 from . import hip_ops
 from . import impala as impala_ops
+from . import mlp as mlp_ops
+from . import nature as nature_ops
 
 PAD_HEAD = 32   # padded output width for the A-dim and V-dim head GEMMs
 KPAD = 32       # LSTM input features padded to a multiple of 32
+
+
+def _encoder_ops(enc):
+    """The ops module serving an encoder: each has Pack, prepare_obs,
+    fwd_pair, fwd and bwd."""
+    if isinstance(enc, ImpalaCNN):
+        return impala_ops
+    return mlp_ops if isinstance(enc, MLPEncoder) else nature_ops
 
 
 def conv1_channels(encoder):
@@ -126,6 +136,8 @@ class _NetPack:
         self.A = A
         self.with_bwd = with_bwd
         self._fast = None
+        # the encoder's own pack (ops/nature.py, impala.py or mlp.py)
+        self.enc_pack = None
         self.refresh()
 
     def refresh(self):
@@ -206,37 +218,10 @@ class _NetPack:
         to_bf = lambda t: t.detach().to(dev).bfloat16().contiguous()
         f32 = lambda t: t.detach().to(dev).float().contiguous()
 
-        self.impala = isinstance(enc, ImpalaCNN)
-        self.mlp = isinstance(enc, MLPEncoder)
-        if self.impala:
-            if hasattr(self, "imp"):
-                self.imp.refresh()
-            else:
-                self.imp = impala_ops.ImpalaPack(enc, dev, self.with_bwd)
-        elif self.mlp:
-            # fc1 stays f32 (the mlp_in kernels read it as it is); fc2 in
-            # the GEMMs' bf16 layouts, (N, K) forward and (K, N) dgrad
-            self.mw1, self.mb1 = f32(enc.fc1.weight), f32(enc.fc1.bias)
-            self.mw2t, self.mb2 = to_bf(enc.fc2.weight), f32(enc.fc2.bias)
-            if self.with_bwd:
-                self.mw2_kn = self.mw2t.t().contiguous()       # (512, 512)
+        if self.enc_pack is None:
+            self.enc_pack = _encoder_ops(enc).Pack(enc, dev, self.with_bwd)
         else:
-            # convs: (COUT, CIN, KH, KW) -> (COUT, KH*KW*CIN)
-            def pack_conv(conv):
-                w = conv.weight.detach()
-                wt = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-                return to_bf(wt), f32(conv.bias)
-
-            self.w1t, self.b1 = pack_conv(enc.conv1)
-            self.w2t, self.b2 = pack_conv(enc.conv2)
-            self.w3t, self.b3 = pack_conv(enc.conv3)
-
-            # FC: torch flattens NCHW (64,7,7); conv3 output flattens HWC
-            wf = enc.fc.weight.detach()          # (512, 3136) over (c,h,w)
-            wf_hwc = (wf.reshape(512, 64, 7, 7).permute(0, 2, 3, 1)
-                      .reshape(512, 3136))
-            self.wft = to_bf(wf_hwc)
-            self.bf = f32(enc.fc.bias)
+            self.enc_pack.refresh()
 
         # LSTM: weight_ih (4H, 512+A+1) padded to KPAD multiple
         wih = net.recurrent.weight_ih_l0.detach()
@@ -267,35 +252,12 @@ class _NetPack:
 
         if self.with_bwd:
             # dgrad prepacks (W stored (K, N))
-            if not (self.impala or self.mlp):
-                self.wf_kn = self.wft.t().contiguous()         # (3136, 512)
             self.wih_kn = self.wih_t.t().contiguous()          # (kin_pad, 4H)
             self.whh_bwd = self.whh_t.t().contiguous()         # (H, 4H)
             self.wa1_kn = self.wa1t.t().contiguous()
             self.wa2_kn = self.wa2t.t().contiguous()           # (512, PAD)
             self.wv1_kn = self.wv1t.t().contiguous()
             self.wv2_kn = self.wv2t.t().contiguous()
-            if self.impala or self.mlp:
-                return
-            # nature conv dgrad prepacks
-            w3 = enc.conv3.weight.detach().to(dev)             # (64,64,3,3)
-            w3_nhwc = w3.permute(0, 2, 3, 1)                   # (co,dy,dx,ci)
-            self.w3d = (w3_nhwc.permute(3, 1, 2, 0)            # (ci,dy,dx,co)
-                        .reshape(64, 9 * 64).bfloat16().contiguous())
-            # conv2 (stride 2): one (ci, tap, co) slab per parity class
-            # (py, px), at index 2*py + px of a single tensor; the class's
-            # taps are dy = py, py+2 (outer) by dx = px, px+2
-            w2 = enc.conv2.weight.detach().to(dev)             # (64,32,4,4)
-            w2_nhwc = w2.permute(0, 2, 3, 1)                   # (co,dy,dx,ci)
-            slabs = []
-            for py in range(2):
-                for px in range(2):
-                    tap_list = [(dy, dx) for dy in range(py, 4, 2)
-                                for dx in range(px, 4, 2)]
-                    wd = torch.stack([w2_nhwc[:, d, x, :] for d, x in tap_list],
-                                     dim=0)                    # (t, co, ci)
-                    slabs.append(wd.permute(2, 0, 1).reshape(32, 4 * 64))
-            self.w2d = torch.stack(slabs).bfloat16().contiguous()  # (4,32,256)
 
 
 # batch rows of the persistent LSTM: one pass up to LSTM_SINGLE_ROWS
@@ -338,6 +300,8 @@ class HipNetworkEngine:
         self.target = _NetPack(target_net, self.device, self.A, with_bwd=False)
         self.online_net = online_net
         self.target_net = target_net
+        self.enc_ops = _encoder_ops(online_net.encoder)
+        self._enc_ws = {}   # the encoder backward's step-to-step scratch
         self.bar = torch.zeros(512, dtype=torch.int32, device=self.device)
         self._empty = torch.Tensor()
         # persistent-LSTM watchdog: the kernels poison GridBar.poison (int32
@@ -387,24 +351,6 @@ class HipNetworkEngine:
         # per-step repack -> ONE gather kernel per dtype (maps bit-probed
         # from the now-flat param buffer; see _NetPack.enable_fast_refresh)
         self.online.enable_fast_refresh(self.flat_param, self.m)
-        # hipGraph capture of the fwd+bwd launch sequence — MEASURED
-        # NEGATIVE, default off (R2D2_HIP_GRAPH=1 to enable):
-        # - prebuilt batches: 11.41k vs 11.54k seq/s uncaptured (the ~55
-        #   launches are already async-submitted; replay saves nothing);
-        # - with the GPU-resident replay in the loop it collapses to ~2.8k:
-        #   the graph's private memory pool evicts the caching allocator's
-        #   blocks for the per-sample gather outputs, degenerating into
-        #   hipMalloc churn.
-        # Kept (capture-correct, all tests pass with it on) for future
-        # launch-bound configs; finding a real ROCm defect on the way: a
-        # captured hipMemsetAsync replays a garbage fill value from the
-        # 2nd replay (gpurun_out/graph_probe2.log) — the LSTM workspace
-        # reset is a plain kernel now (zero_gridbar_kernel).
-        self._graph = None
-        self._graph_key = None
-        # (bypassed for the mlp encoder: never captured with it)
-        self._use_graph = (os.environ.get("R2D2_HIP_GRAPH", "0") == "1"
-                           and not self.timing and not self.mlp)
 
     def _mark(self, name):
         if self.timing:
@@ -435,80 +381,11 @@ class HipNetworkEngine:
         self.target.refresh()
 
     # ------------------------------------------------------------------
+    # nature encoder: 0 runs the classic tiled forwards, twice
     _fwd_band = os.environ.get("R2D2_CONV_FWD_BAND", "1") != "0"
     # conv wgrads flush per-workgroup partial sums with plain stores and one
     # reducer per layer writes .grad; 0 keeps the atomic flush + copies
     _wgrad_slab = os.environ.get("R2D2_CONV_WGRAD_SLAB", "1") != "0"
-    _wgrad_ws = None
-
-    def _conv_bwd_slab(self, enc, ON, dflat3, a1, a2, obs_hwc, M):
-        """Nature-CNN conv backward on the slab path.  Every dY is already
-        masked (by the FC dgrad's and the conv dgrads' stores), so the wgrads
-        get no mask to re-read; each reducer overwrites its .grad views of
-        the flat buffer in torch layout, so nothing is zeroed or copied."""
-        m = self.m
-        band1 = self.C == 4
-        need = max(m.conv_wgrad_ws_floats(3, 0, M, True),
-                   m.conv_wgrad_ws_floats(2, 0, M, True),
-                   m.conv_wgrad_ws_floats(1, self.C, M, band1))
-        if self._wgrad_ws is None or self._wgrad_ws.numel() < need:
-            # one partial-sum workspace for the three layers (they run one
-            # after the other), kept from step to step
-            self._wgrad_ws = torch.empty(need, dtype=torch.float32,
-                                         device=self.device)
-        ws, no_mask = self._wgrad_ws, self._empty
-        m.conv_wgrad_band_into(dflat3, no_mask, a2, 3, M, ws,
-                               enc.conv3.weight.grad, enc.conv3.bias.grad)
-        d_a2 = m.conv_dgrad_band(dflat3, ON.w3d, a2, 3, M)
-        d_a2f = d_a2.view(M * 81, 64)
-        m.conv_wgrad_band_into(d_a2f, no_mask, a1, 2, M, ws,
-                               enc.conv2.weight.grad, enc.conv2.bias.grad)
-        d_a1 = m.conv_dgrad_band(d_a2f, ON.w2d, a1, 2, M).view(M * 400, 32)
-        # conv1: band with four channels, chunked with one (see below)
-        if band1:
-            m.conv_wgrad_band_into(d_a1, no_mask, obs_hwc, 1, M, ws,
-                                   enc.conv1.weight.grad, enc.conv1.bias.grad)
-        else:
-            m.conv_wgrad_into(d_a1, no_mask, obs_hwc, 1, M, 84, 84, 20, 20,
-                              32, 8 * 8 * self.C, ws, enc.conv1.weight.grad,
-                              enc.conv1.bias.grad)
-
-    def _encoder_fwd(self, pack, obs_hwc_u8, want_stash=True):
-        """obs: (M, 84, 84, C) uint8 -> latent (M, 512) bf16 + stashes.
-        MLP encoder: obs is X (M, D) float32, the stash (X, A1)."""
-        m = self.m
-        if self.mlp:
-            a1 = m.mlp_in_fwd(obs_hwc_u8, pack.mw1, pack.mb1)
-            latent = m.gemm_bias_act(a1, pack.mw2t, pack.mb2, 1, False)
-            return latent, (obs_hwc_u8, a1)
-        if self.impala:
-            return impala_ops.encoder_fwd(m, pack.imp, obs_hwc_u8, want_stash,
-                                          xp=getattr(self, "_xp", None))
-        M = obs_hwc_u8.shape[0]
-        if self._fwd_band:
-            # per-image band forward: image LDS-resident, one global
-            # read/dequant per input element
-            a1 = m.conv_fwd_band(obs_hwc_u8, pack.w1t, pack.b1, 1, M)
-        else:
-            a1 = m.conv_fwd(obs_hwc_u8, pack.w1t, pack.b1, 1, M, 84, 84,
-                            20, 20, True)
-        return self._encoder_from_a1(pack, a1)
-
-    def _encoder_from_a1(self, pack, a1):
-        """Nature encoder above conv1: a1 (M*400, 32) bf16 -> latent (M, 512)
-        bf16 + stashes.  conv1 runs once for the online and the target
-        network in the train step (conv1_fwd_dual), so it is not in here."""
-        m = self.m
-        M = a1.shape[0] // 400
-        if self._fwd_band:
-            a2 = m.conv_fwd_band(a1, pack.w2t, pack.b2, 2, M)
-            a3 = m.conv_fwd_band(a2, pack.w3t, pack.b3, 3, M)
-        else:
-            a2 = m.conv_fwd(a1, pack.w2t, pack.b2, 2, M, 20, 20, 9, 9, True)
-            a3 = m.conv_fwd(a2, pack.w3t, pack.b3, 3, M, 9, 9, 7, 7, True)
-        flat = a3.view(M, 3136)
-        latent = m.gemm_bias_act(flat, pack.wft, pack.bf, 1, False)
-        return latent, (a1, a2, a3, flat)
 
     def _lstm_input(self, pack, latent, last_action, last_reward):
         """Build padded rin (one fused kernel) and the input-GEMM X."""
@@ -538,16 +415,14 @@ class HipNetworkEngine:
         arrays indexing (b * (T+1) + t + 1) rows of Hout, plus per-row b,t
         (for the dHext scatter).  Cached by batch layout — fixed-shape
         batches (the common case) skip the python loop and re-upload."""
-        key = (T, burn.numpy().tobytes(), learn.numpy().tobytes(),
-               fwd.numpy().tobytes())
+        bu, le, fw = burn.numpy(), learn.numpy(), fwd.numpy()
+        key = (T, bu.tobytes(), le.tobytes(), fw.tobytes())
         if self._pos_cache is None:
             self._pos_cache = {}
         if key in self._pos_cache:
             return self._pos_cache[key]
         n = self.cfg.forward_steps
-        bu = burn.numpy().astype(np.int64)
-        le = learn.numpy().astype(np.int64)
-        fw = fwd.numpy().astype(np.int64)
+        bu, le, fw = (v.astype(np.int64) for v in (bu, le, fw))
         R = int(le.sum())
         # vectorized ragged expansion (no per-sample python loop)
         b_of = np.repeat(np.arange(len(le), dtype=np.int64), le)
@@ -578,107 +453,28 @@ class HipNetworkEngine:
         return out
 
     # ------------------------------------------------------------------
-    # -- hipGraph capture ----------------------------------------------
-    def _layout_key(self, batch):
-        return (tuple(batch.obs.shape), batch.obs.dtype,
-                batch.burn_in_steps.numpy().tobytes(),
-                batch.learning_steps.numpy().tobytes(),
-                batch.forward_steps.numpy().tobytes())
-
-    def _copy_into_static(self, batch):
-        sb = self._static_batch
-        for f in ("obs", "last_action", "last_reward", "hidden", "action",
-                  "n_step_reward", "gamma", "is_weights"):
-            getattr(sb, f).copy_(getattr(batch, f), non_blocking=True)
-
-    def _try_capture(self, batch, key):
-        import types
-        dev = self.device
-        sb = types.SimpleNamespace(
-            obs=batch.obs.to(dev).contiguous().clone(),
-            last_action=batch.last_action.to(dev).contiguous().clone(),
-            last_reward=batch.last_reward.to(dev).contiguous().clone(),
-            hidden=batch.hidden.to(dev).contiguous().clone(),
-            action=batch.action.to(dev).contiguous().clone(),
-            n_step_reward=batch.n_step_reward.to(dev).contiguous().clone(),
-            gamma=batch.gamma.to(dev).contiguous().clone(),
-            is_weights=batch.is_weights.to(dev).contiguous().clone(),
-            burn_in_steps=batch.burn_in_steps,
-            learning_steps=batch.learning_steps,
-            forward_steps=batch.forward_steps)
-        try:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):                  # allocator warmup
-                    self._train_step_impl(sb)
-            torch.cuda.current_stream().wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            # thread_local: the replay-ingest thread keeps streaming actor
-            # blocks on its own streams while we capture — global capture
-            # mode would invalidate them and poison the whole HIP context
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                loss, prio = self._train_step_impl(sb)
-        except Exception as e:
-            print(f"[engine] hipGraph capture failed ({e!r}); "
-                  f"running uncaptured", flush=True)
-            self._use_graph = False
-            return False
-        self._graph = g
-        self._graph_key = key
-        self._static_batch = sb
-        self._graph_out = (loss, prio)
-        return True
-
     def train_step(self, batch, grad_hook=None):
-        """Full fused update (hipGraph replay when the batch layout matches
-        the captured graph).  Fills .grad on the online nn.Module params
+        """Full fused update.  Fills .grad on the online nn.Module params
         and returns (loss tensor, per-sequence priority tensor, both on
         device).  ``grad_hook(segment)`` fires when a flat-grad segment
         ("heads", "lstm", "encoder") is complete — the DP learner uses it
         to overlap the RCCL all-reduce with the rest of the manual
-        backward (graphs are bypassed in that case so the collectives can
-        interleave)."""
+        backward."""
         check_batch_size(batch.obs.shape[0], "the batch's B")
         if bool(self._poison_pin.any()):
             raise RuntimeError(
                 "persistent LSTM kernel poisoned on a previous step "
                 "(bounded-spin timeout) — outputs/gradients of that step "
                 "are invalid; aborting instead of training on them")
-        if self._use_graph and grad_hook is None:
-            key = self._layout_key(batch)
-            if self._graph_key != key:
-                self._try_capture(batch, key)
-            if self._graph_key == key:
-                # capture only RECORDS the work — every step (including the
-                # capture step) must replay to actually execute
-                self._copy_into_static(batch)
-                self._graph.replay()
-                return self._graph_out
-        return self._train_step_impl(batch, grad_hook)
-
-    def _train_step_impl(self, batch, grad_hook=None):
-        """The uncaptured launch sequence (also the capture body)."""
         m = self.m
         c = self.cfg
         dev = self.device
         B, T = batch.obs.shape[:2]
         A, H = self.A, self.H
+        enc_ops = self.enc_ops
 
         # ---- inputs ----------------------------------------------------
-        obs = batch.obs
-        if self.mlp:
-            # (B, T, D) float32 vector observations: X (M, D), no dequant
-            if obs.dtype != torch.float32 or tuple(obs.shape[2:]) != (self.C,):
-                raise TypeError(
-                    f"the mlp encoder takes (B, T, {self.C}) float32 "
-                    f"observations, got {tuple(obs.shape)} {obs.dtype}")
-            obs_hwc = obs.reshape(B * T, self.C).contiguous()
-        elif obs.shape[-1] == self.C and obs.shape[2] == 84:   # already HWC
-            obs_hwc = obs.reshape(B * T, 84, 84, self.C)
-        else:                                      # (B,T,C,84,84) -> NHWC
-            obs_hwc = obs.permute(0, 1, 3, 4, 2).reshape(B * T, 84, 84, self.C)
-            obs_hwc = obs_hwc.contiguous()
+        obs = enc_ops.prepare_obs(batch.obs, B, T, self.C)
         la = batch.last_action.to(dev)
         lr = batch.last_reward.to(dev)
         md = getattr(batch, "meta_dev", None)
@@ -699,26 +495,9 @@ class HipNetworkEngine:
 
         self._mark("start")
         # ---- forward ---------------------------------------------------
-        if self.impala:
-            # pack frames once; online and target share the padded u8 tensor
-            self._xp = impala_ops.pack_obs(m, self.online.imp, obs_hwc)
-        if self._fwd_band and not (self.mlp or self.impala):
-            # both networks' conv1 from one staging of each frame
-            a1_o, a1_t = m.conv1_fwd_dual(
-                obs_hwc, self.online.w1t, self.online.b1, self.target.w1t,
-                self.target.b1, B * T)
-            self._mark("conv1_dual")
-            lat_o, enc_stash = self._encoder_from_a1(self.online, a1_o)
-            self._mark("enc_online")
-            lat_t, _ = self._encoder_from_a1(self.target, a1_t)
-            del a1_t                    # dead after the target's conv2
-            self._mark("enc_target")
-        else:
-            lat_o, enc_stash = self._encoder_fwd(self.online, obs_hwc)
-            self._mark("enc_online")
-            lat_t, _ = self._encoder_fwd(self.target, obs_hwc,
-                                         want_stash=False)
-            self._mark("enc_target")
+        lat_o, enc_stash, lat_t = enc_ops.fwd_pair(
+            m, self.online.enc_pack, self.target.enc_pack, obs,
+            fwd_band=self._fwd_band, mark=self._mark)
         rin_o, X_o = self._lstm_input(self.online, lat_o, la, lr)
         _, X_t = self._lstm_input(self.target, lat_t, la, lr)
         self._mark("lstm_input")
@@ -813,100 +592,11 @@ class HipNetworkEngine:
         dlat = m.gemm_dgrad(dgates_flat, self._empty, ON.wih_kn, False, 512)
         self._mark("lstm_wgrads")
 
-        M = B * T
-        if self.mlp:
-            # fc2 dgrad with fc2's own relu mask (lat) on load and fc1's
-            # (A1) on store; both wgrads add straight into the .grad views
-            X, a1 = enc_stash
-            enc = net.encoder
-            d_a1 = m.gemm_dgrad(dlat, lat_o, ON.mw2_kn, True, 0, a1)
-            m.gemm_wgrad_into(dlat, lat_o, a1, True, enc.fc2.weight.grad,
-                              enc.fc2.bias.grad)
-            m.mlp_in_wgrad_into(d_a1, X, enc.fc1.weight.grad,
-                                enc.fc1.bias.grad)
-            self._mark("mlp_bwd")
-            if grad_hook is not None:
-                grad_hook("encoder")
-            self._mark("grad_write")
-            return loss.squeeze(0), prio
-        if self.impala:
-            impala_ops.encoder_bwd(m, ON.imp, enc_stash, dlat, lat_o)
-            self._mark("conv_bwd")
-            if grad_hook is not None:
-                grad_hook("encoder")
-            self._mark("grad_write")
-            return loss.squeeze(0), prio
-
-        a1, a2, a3, flat = enc_stash
-        lat_bf = lat_o  # forward output (relu mask source)
-        # FC dgrad with BOTH relu backwards fused: the mask of the FC's own
-        # relu (lat) on load, conv3's relu mask (a3) on store — dflat leaves
-        # this kernel pre-masked, so no elementwise mask/pad passes run on
-        # the conv gradients at all.
-        dflat = m.gemm_dgrad(dlat, lat_bf, ON.wf_kn, True, 0, a3)
-        dWf, dbf = m.gemm_wgrad(dlat, lat_bf, flat, True, True)
-
-        # conv3 backward.  Conv weight grads accumulate in the packed
-        # (COUT, ky, kx, c) layout — torch-layout atomics scatter each
-        # 16-lane wave across 16 cachelines (measured 4-5x slower) — and
-        # are permuted into .grad afterwards (tiny tensors).
-        self._mark("fc_bwd")
-        dflat3 = dflat.view(M * 49, 64)   # pre-masked by a3
-        enc = net.encoder
-        if self._wgrad_slab:
-            self._conv_bwd_slab(enc, ON, dflat3, a1, a2, obs_hwc, M)
-            self._mark("conv_bwd")
-            enc.fc.weight.grad.copy_(
-                dWf.view(512, 7, 7, 64).permute(0, 3, 1, 2).reshape(512, 3136))
-            enc.fc.bias.grad.copy_(dbf)
-            if grad_hook is not None:
-                grad_hook("encoder")
-            self._mark("grad_write")
-            return loss.squeeze(0), prio
-        # R2D2_CONV_WGRAD_SLAB=0: the atomic-flush wgrads (A/B reference)
-        # per-image band wgrads: whole input image staged in LDS once
-        # (single dequant per element; conv1 patch traffic 557 -> 154 MB)
-        dW3, db3 = m.conv_wgrad_band(dflat3, a3, a2, 3, M)
-        # per-image band dgrad (dY staged once in LDS inside a zero halo, no
-        # zero-padded staging copies in memory); the output mask fuses
-        # conv2's relu backward into the d_a2 store
-        d_a2 = m.conv_dgrad_band(dflat3, ON.w3d, a2, 3, M)
-        # conv2 backward (d_a2 pre-masked by a2); all four stride-parity
-        # classes of the dgrad run in the one launch
-        d_a2f = d_a2.view(M * 81, 64)
-        dW2, db2 = m.conv_wgrad_band(d_a2f, a2, a1, 2, M)
-        d_a1 = m.conv_dgrad_band(d_a2f, ON.w2d, a1, 2, M)
-        # conv1 wgrad (no dgrad: input is data; d_a1 pre-masked by a1).
-        # Each channel count runs the kernel measured faster for it, 5440
-        # images, device events, medians of two rounds (docs/STATUS.md):
-        # four channels (K = 256) 0.193 ms band vs 0.246-0.250 ms chunked —
-        # with the fragments gathered from the LDS image the band no longer
-        # pays an im2col copy and two barriers per 32 rows; one channel
-        # (K = 64) 0.116-0.117 ms chunked vs 0.120 ms band — the image is a
-        # quarter of the size, so there is little staging left to save.
-        if self.C == 4:
-            dW1, db1 = m.conv_wgrad_band(d_a1.view(M * 400, 32), a1,
-                                         obs_hwc, 1, M)
-        else:
-            dW1, db1 = m.conv_wgrad(d_a1.view(M * 400, 32), a1, obs_hwc, 1,
-                                    M, 84, 84, 20, 20, 32, 8 * 8 * self.C)
-        self._mark("conv_bwd")
-
-        def conv_grad(dwt, cout, kh, kw, cin):
-            return dwt.view(cout, kh, kw, cin).permute(0, 3, 1, 2)
-
-        enc.conv1.weight.grad.copy_(conv_grad(dW1, 32, 8, 8, self.C))
-        enc.conv1.bias.grad.copy_(db1)
-        enc.conv2.weight.grad.copy_(conv_grad(dW2, 64, 4, 4, 32))
-        enc.conv2.bias.grad.copy_(db2)
-        enc.conv3.weight.grad.copy_(conv_grad(dW3, 64, 3, 3, 64))
-        enc.conv3.bias.grad.copy_(db3)
-        enc.fc.weight.grad.copy_(
-            dWf.view(512, 7, 7, 64).permute(0, 3, 1, 2).reshape(512, 3136))
-        enc.fc.bias.grad.copy_(dbf)
+        enc_ops.bwd(m, ON.enc_pack, net.encoder, enc_stash, dlat, lat_o, obs,
+                    wgrad_slab=self._wgrad_slab, mark=self._mark,
+                    ws=self._enc_ws)
         if grad_hook is not None:
             grad_hook("encoder")
-
         self._mark("grad_write")
         return loss.squeeze(0), prio
 
@@ -935,17 +625,14 @@ class HipInference:
         self.m = hip_ops.ext(required=True)
         self.net = net
         self.pack = _NetPack(net, self.device, self.A, with_bwd=False)
-        self.impala = self.pack.impala
-        self.mlp = self.pack.mlp
+        self.enc_ops = _encoder_ops(net.encoder)
 
     def refresh(self):
         self.pack.refresh()
 
-    def _mlp_latent(self, obs):
-        """obs (E, D) float32 on device -> latent (E, 512) bf16."""
-        p = self.pack
-        a1 = self.m.mlp_in_fwd(obs.contiguous(), p.mw1, p.mb1)
-        return self.m.gemm_bias_act(a1, p.mw2t, p.mb2, 1, False)
+    def _latent(self, obs):
+        """obs as `forward` takes it -> latent (E, 512) bf16."""
+        return self.enc_ops.fwd(self.m, self.pack.enc_pack, obs)
 
     @torch.no_grad()
     def forward(self, obs_u8_nchw, last_action, last_reward, hidden):
@@ -955,18 +642,7 @@ class HipInference:
         (h', c'))."""
         m = self.m
         E = obs_u8_nchw.shape[0]
-        obs_hwc = (None if self.mlp
-                   else obs_u8_nchw.permute(0, 2, 3, 1).contiguous())
-        if self.mlp:
-            lat = self._mlp_latent(obs_u8_nchw)
-        elif self.impala:
-            lat, _ = impala_ops.encoder_fwd(m, self.pack.imp, obs_hwc, False)
-        else:
-            p = self.pack
-            a1 = m.conv_fwd(obs_hwc, p.w1t, p.b1, 1, E, 84, 84, 20, 20, True)
-            a2 = m.conv_fwd(a1, p.w2t, p.b2, 2, E, 20, 20, 9, 9, True)
-            a3 = m.conv_fwd(a2, p.w3t, p.b3, 3, E, 9, 9, 7, 7, True)
-            lat = m.gemm_bias_act(a3.view(E, 3136), p.wft, p.bf, 1, False)
+        lat = self._latent(obs_u8_nchw)
         p = self.pack
         rin = m.assemble_rin(lat.contiguous(),
                              last_action.float().contiguous(),
@@ -1002,18 +678,7 @@ class HipInference:
         storage."""
         m = self.m
         E = obs_u8_nchw.shape[0]
-        obs_hwc = (None if self.mlp
-                   else obs_u8_nchw.permute(0, 2, 3, 1).contiguous())
-        if self.mlp:
-            lat = self._mlp_latent(obs_u8_nchw)
-        elif self.impala:
-            lat, _ = impala_ops.encoder_fwd(m, self.pack.imp, obs_hwc, False)
-        else:
-            p = self.pack
-            a1 = m.conv_fwd(obs_hwc, p.w1t, p.b1, 1, E, 84, 84, 20, 20, True)
-            a2 = m.conv_fwd(a1, p.w2t, p.b2, 2, E, 20, 20, 9, 9, True)
-            a3 = m.conv_fwd(a2, p.w3t, p.b3, 3, E, 9, 9, 7, 7, True)
-            lat = m.gemm_bias_act(a3.view(E, 3136), p.wft, p.bf, 1, False)
+        lat = self._latent(obs_u8_nchw)
         p = self.pack
         h0, c0 = hidden
         dev = lat.device

@@ -7,14 +7,20 @@ halo-padded NHWC activations, MFMA implicit-GEMM 3x3 convs whose dgrad is
 the same kernel with flipped prepacked weights, fused pre-activation
 ReLU / residual epilogues, and an atomic-free maxpool backward.
 
-The engine (ops/engine.py) delegates encoder fwd/bwd here when
-config.encoder == 'impala'; LSTM / heads / loss / optimizer paths are
-shared with the flagship nature config.
+Same interface as ops/nature.py and ops/mlp.py (pack, `prepare_obs`,
+`fwd_pair`, `fwd`, `bwd`); LSTM / heads / loss / optimizer paths are shared
+with the flagship nature config.
 """
 
+import os
 from typing import Optional
 
 import torch
+
+from .nature import prepare_obs  # noqa: F401  (the same u8 frames)
+
+# 0: stage conv and maxpool as two kernels (the fused kernel's oracle)
+_FUSED_POOL = os.environ.get("R2D2_IMPALA_FUSED_POOL", "1") != "0"
 
 # stage geometry: (conv-input H, pooled H) per stage; 84 -> 42 -> 21 -> 11
 STAGES = ((84, 42), (42, 21), (21, 11))
@@ -107,6 +113,9 @@ class ImpalaPack:
             self.wf_kn = self.wft.t().contiguous()
 
 
+Pack = ImpalaPack
+
+
 def pack_obs(m, pack: ImpalaPack, obs_hwc_u8: torch.Tensor) -> torch.Tensor:
     """Frames -> halo-padded 8-channel u8 via the pack's arena; call once
     per step and share between the online and target forward passes."""
@@ -132,13 +141,11 @@ def encoder_fwd(m, pack: ImpalaPack, obs_hwc_u8: torch.Tensor,
     st = {"xp": xp} if want_stash else None
     x = xp
     empty = torch.Tensor()
-    import os
-    fused_pool = os.environ.get("R2D2_IMPALA_FUSED_POOL", "1") != "0"
     for si, (hin, hout) in enumerate(STAGES):
         c = CHANS[si]
         pooled = ar.get("fwd", (M, hout + 2, hout + 2, c))
         arg = ar.get("fwd", (M, hout, hout, c), torch.uint8)
-        if fused_pool:
+        if _FUSED_POOL:
             # stage conv + maxpool in one kernel: the (hin+2)^2 conv output
             # stays in LDS (s0 alone: ~2.6 GB/step of HBM traffic saved
             # across both nets; docs/IMPALA_ROOFLINE.md)
@@ -171,6 +178,28 @@ def encoder_fwd(m, pack: ImpalaPack, obs_hwc_u8: torch.Tensor,
     if want_stash:
         st["flat"] = flat
     return latent, st
+
+
+def fwd_pair(m, online, target, obs, *, fwd_band, mark):
+    """Both networks -> (lat_o, online stash, lat_t); the frames are packed
+    once and the padded u8 tensor is shared."""
+    xp = pack_obs(m, online, obs)
+    lat_o, stash = encoder_fwd(m, online, obs, True, xp=xp)
+    mark("enc_online")
+    lat_t, _ = encoder_fwd(m, target, obs, False, xp=xp)
+    mark("enc_target")
+    return lat_o, stash, lat_t
+
+
+def fwd(m, pack, obs):
+    """Actor inference: obs (E, 4, 84, 84) u8 -> latent (E, hidden) bf16."""
+    return encoder_fwd(m, pack, obs.permute(0, 2, 3, 1).contiguous(),
+                       False)[0]
+
+
+def bwd(m, pack, enc, stash, dlat, lat_o, obs, *, wgrad_slab, mark, ws):
+    encoder_bwd(m, pack, stash, dlat, lat_o)
+    mark("conv_bwd")
 
 
 def encoder_bwd(m, pack: ImpalaPack, st: dict, dlat: torch.Tensor,

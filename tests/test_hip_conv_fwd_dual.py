@@ -205,7 +205,8 @@ def test_engine_step_matches_classic_forward(preset):
             eng.flat_param.add_(torch.randn(
                 eng.flat_param.shape, device="cuda", generator=g) * 0.01)
         eng.refresh_online()
-        assert not torch.equal(eng.online.w1t, eng.target.w1t)
+        assert not torch.equal(eng.online.enc_pack.w1t,
+                               eng.target.enc_pack.w1t)
         batch = build_batch(c, torch.device("cuda"), seed=5)
         assert batch.obs.shape[:2] == (8, 7)
         loss, prio = eng.train_step(batch)

@@ -183,11 +183,12 @@ def test_fast_refresh_matches_python_repack():
                   for n, h, a, k in _pack_items(engine.online)}
     ref_items = {n: _item_get(h, a, k) for n, h, a, k in _pack_items(ref)}
     assert set(fast_items) == set(ref_items)
-    assert {"mw1", "mb1", "mw2t", "mb2", "mw2_kn"} <= set(fast_items)
+    assert {"enc_pack.mw1", "enc_pack.mb1", "enc_pack.mw2t", "enc_pack.mb2",
+            "enc_pack.mw2_kn"} <= set(fast_items)
     for n, t in fast_items.items():
         assert torch.equal(t, ref_items[n].view(t.shape)), n
-    assert fast_items["mw1"].dtype == torch.float32
-    assert bits_equal(fast_items["mw1"],
+    assert fast_items["enc_pack.mw1"].dtype == torch.float32
+    assert bits_equal(fast_items["enc_pack.mw1"],
                       engine.online_net.encoder.fc1.weight.detach())
 
 
@@ -201,7 +202,8 @@ def test_weight_bus_roundtrip():
     other = make_net(c, 99).cuda()
     inf = HipInference(other, torch.device("cuda"), c)
     before = {n: t.clone() for n, t in pack_tensors(inf.pack).items()}
-    assert {"mw1", "mb1", "mw2t", "mb2"} <= set(before)
+    assert {"enc_pack.mw1", "enc_pack.mb1", "enc_pack.mw2t",
+            "enc_pack.mb2"} <= set(before)
     bus.publish(engine.online)
     ver = bus.pull_into(inf.pack, 0)
     assert ver == 2
@@ -210,7 +212,8 @@ def test_weight_bus_roundtrip():
     assert set(dst) == set(pack_tensors(engine.target))
     for name, t in dst.items():
         assert bits_equal(t, src[name].view(t.shape)), name
-    for name in ("mw1", "mb1", "mw2t", "mb2"):
+    for name in ("enc_pack.mw1", "enc_pack.mb1", "enc_pack.mw2t",
+                 "enc_pack.mb2"):
         assert not torch.equal(dst[name], before[name]), name
 
 
@@ -302,12 +305,12 @@ def test_inference_matches_network_forward(E):
     lat_s, = inf.m.latents["lstm_cell_step"]
     assert bits_equal(lat_f, lat_s), "same encoder calls, same latent"
 
-    p = inf.pack
-    a1_64 = torch.relu(obs.double() @ p.mw1.double().t() + p.mb1.double())
-    a1_32 = torch.relu(obs @ p.mw1.t() + p.mb1).bfloat16()
-    lat_64 = torch.relu(a1_64 @ p.mw2t.double().t() + p.mb2.double())
-    lat_32 = torch.relu(a1_32.float() @ p.mw2t.float().t()
-                        + p.mb2).bfloat16()
+    p, e = inf.pack, inf.pack.enc_pack
+    a1_64 = torch.relu(obs.double() @ e.mw1.double().t() + e.mb1.double())
+    a1_32 = torch.relu(obs @ e.mw1.t() + e.mb1).bfloat16()
+    lat_64 = torch.relu(a1_64 @ e.mw2t.double().t() + e.mb2.double())
+    lat_32 = torch.relu(a1_32.float() @ e.mw2t.float().t()
+                        + e.mb2).bfloat16()
     ek, em = rel_err(lat_s, lat_64), rel_err(lat_32, lat_64)
     print(f"CALIB latent E{E}: kernel {ek:.3e} yardstick {em:.3e}")
     assert ek <= FACTOR * em, (ek, em)

@@ -46,7 +46,7 @@ def test_engine_is_built_for_single_frame():
     c, eager, hip = make_learners()
     assert hip.engine is not None
     assert hip.engine.C == 1
-    assert hip.engine.online.w1t.shape == (32, 64)
+    assert hip.engine.online.enc_pack.w1t.shape == (32, 64)
     assert eager.engine is None
 
 
@@ -113,7 +113,7 @@ def test_fast_refresh_matches_python_repack():
     ref_items = {n: _item_get(h, a, k)
                  for n, h, a, k in _pack_items(ref)}
     assert set(fast_items) == set(ref_items)
-    assert fast_items["w1t"].shape == (32, 64)
+    assert fast_items["enc_pack.w1t"].shape == (32, 64)
     for n, t in fast_items.items():
         assert torch.equal(t, ref_items[n].view(t.shape)), n
 
@@ -170,7 +170,7 @@ def test_weight_bus_roundtrip():
                     encoder=c.encoder, forward_steps=c.forward_steps,
                     mlp_hidden=c.mlp_hidden).cuda()
     inf = HipInference(other, torch.device("cuda"), c)
-    assert inf.pack.w1t.shape == (32, 64)
+    assert inf.pack.enc_pack.w1t.shape == (32, 64)
 
     before = {n: t.clone() for n, t in pack_tensors(inf.pack).items()}
     bus.publish(engine.online)
